@@ -17,8 +17,12 @@ all_reduce(SUM)'d and the per-shard top-k lists all_gather'ed and merged (RCCL).
 Rank 0 prints ONE JSON line: the driver contract plus
   "roofline"     -- dominant kernel (largest share of device time), algorithmic FLOP per launch / measured
                     launch duration (HIP events on the launch stream, taken inside the timed steps);
-  "cpu_baseline" -- the CPU oracle (a port, not the product) timed on the host cores on a bounded sample
-                    of the same pass.
+  "cpu_baseline" -- (--full only) the CPU oracle (a port, not the product) timed on the host cores on a bounded
+                    sample of the same pass.
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds everything else after the timed
+region: the CPU baseline and the parity check against the oracle, and the sub-records (bf16 scoring, small query
+batches, planted queries, VGG19 extractor, the reference's loop on the host, the DiDeMo shapes in child processes).
+`--dump-outputs DIR` writes the last timed step's outputs (ranks, top-k distances and ids) to DIR/<name>.npy.
 """
 import argparse
 import json
@@ -48,8 +52,14 @@ def parse():
     ap.add_argument("--queries", type=int, default=5000)
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--feat-dim", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the bf16 / small-batch / VGG sub-records measured after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline + parity check and the sub-records (bf16, small batches, "
+                         "planted queries, VGG, host loop, DiDeMo shapes); off: the run times the steps and prints the line, nothing more")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, at most 64 MB: above that a "
+                         "fixed seeded sample of the queries, their row numbers in query_rows.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the sub-records measured after the timed steps")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="vfr_set_option passthrough for parameter sweeps (results must not change: compare the checksums)")
     ap.add_argument("--host-feed", action="store_true",
@@ -58,7 +68,10 @@ def parse():
     ap.add_argument("--plant-alpha", type=float, default=0.5, help="noise scale of the planted-query sub-record (realistic_gt)")
     ap.add_argument("--cpu-queries", type=int, default=1024, help="queries of the batch the CPU oracle leg runs (against ALL videos)")
     ap.add_argument("--parity-ranks", type=int, default=64, help="queries whose ground-truth rank counts the oracle recomputes")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # profiler sites -> the kernel they launch (the dominant kernel is chosen per KERNEL: the scorer's ladder stages B and C
@@ -121,6 +134,33 @@ def host_cores():
     except AttributeError:
         avail = total
     return min(avail, int(os.environ.get("VFR_BENCH_CPU_THREADS", "16"))), total
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """`--dump-outputs`: what the pass returns to its caller after the last timed step -- ranks [2, Nq] (0-based position of
+    the best ground-truth moment at IoU 0.5 / 0.7), top-k distances [Nq, k] and moment ids [Nq, k] -- as DIR/<name>.npy,
+    float32 distances, float64 ranks / ids (exact: every id < 2^53).  Above 64 MB in all, a fixed seeded sample of the
+    queries (the same rows in every array) is written and its row numbers as query_rows.npy."""
+    ranks, dist, idx = (None if t is None else t.cpu().numpy() for t in out)
+    nq = ranks.shape[1]
+    per_query = 8 * ranks.shape[0] + (12 * dist.shape[1] if dist is not None else 0) + 8
+    budget = DUMP_BYTES - 4096                                  # room for the .npy headers
+    rows = None
+    if nq * per_query > budget:
+        rows = np.sort(np.random.default_rng(0).choice(nq, budget // per_query, replace=False))
+    arrays = {"ranks": (ranks if rows is None else ranks[:, rows]).astype(np.float64)}
+    if dist is not None:
+        arrays["topk_distances"] = (dist if rows is None else dist[rows]).astype(np.float32)
+        arrays["topk_ids"] = (idx if rows is None else idx[rows]).astype(np.float64)
+    if rows is not None:
+        arrays["query_rows"] = rows.astype(np.float64)
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a))
 
 
 def cpu_baseline_and_parity(args, n_clips, seg, ctx, clip_off, tokens, sd, own, times, counts_all, gpu_out, gpu_emb, gpu_Q):
@@ -352,6 +392,8 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
 
     ms_step = dt * 1e3 / args.steps
     value = Nq * Nv / (dt / args.steps)
@@ -437,9 +479,9 @@ def main():
         line["accounting_notes"] = accounting_notes
     if host_feed is not None:
         line["pcie_inclusive"] = host_feed
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         line.update(extras(args, dev, model, seg, ctx, clip_off, tokens, make_shard, ranks_of, out, Nq, Nv, counts_all, ops))
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # rank 0 at N = 1 only; the CPU leg doubles as the in-run parity check the metric names ("+ rank@1/5 vs CPU ref")
         line["cpu_baseline"], line["parity"] = cpu_baseline_and_parity(args, n_clips, seg, ctx, clip_off, tokens, sd, own, times, counts_all,
                                                                        out, state["shard"].bank.emb, state["Q"])

@@ -13,6 +13,10 @@ import torch.multiprocessing as mp
 
 from helpers import MemoryDataset, make_model, problem
 
+# the ranks and the single-process reference run the CPU encoders on ONE thread: with more, some hosts' CPU GEMM / LSTM
+# kernels give bits that depend on the thread count and on the batch (a rank encodes only its slice of the queries)
+CPU_THREADS = 1
+
 
 def _free_port():
     with socket.socket() as s:
@@ -22,7 +26,7 @@ def _free_port():
 
 def _worker(rank, world, port, clips, out_dir, sample=256, force=False):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.set_num_threads(2)
+    torch.set_num_threads(CPU_THREADS)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         from vfr_amd import engine
@@ -50,11 +54,16 @@ def test_two_rank_sharded_evaluate_equals_single_process(tmp_path, clips, sample
     mp.spawn(_worker, args=(world, _free_port(), clips, str(tmp_path), sample, world == 1), nprocs=world, join=True)
     p = problem(37, 23, clips, feat_dim=64, hidden=16)
     ds = MemoryDataset(p["seg"], p["ctx"], p["counts"], p["tokens"], p["own"], p["times"])
-    vi, li = ds.iterators()
-    ref_metrics, (rd, ri) = vevaluate.evaluate(make_model(p["sd"], feat_dim=64, hidden=16), vi, li, ds.annotations,
-                                               "cpu", return_topk=50)
-    vi, li = ds.iterators()
-    ref_val = vevaluate.validate_epoch(make_model(p["sd"], feat_dim=64, hidden=16), vi, li, ds.annotations, "cpu", size=-1)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(CPU_THREADS)
+    try:
+        vi, li = ds.iterators()
+        ref_metrics, (rd, ri) = vevaluate.evaluate(make_model(p["sd"], feat_dim=64, hidden=16), vi, li, ds.annotations,
+                                                   "cpu", return_topk=50)
+        vi, li = ds.iterators()
+        ref_val = vevaluate.validate_epoch(make_model(p["sd"], feat_dim=64, hidden=16), vi, li, ds.annotations, "cpu", size=-1)
+    finally:
+        torch.set_num_threads(threads)
     for r in range(world):
         got = np.load(tmp_path / f"r{r}.npz")
         assert json.loads(str(got["metrics"])) == json.loads(json.dumps(ref_metrics))

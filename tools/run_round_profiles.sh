@@ -4,7 +4,7 @@
 tag=${1:-r2}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 o=gpurun_out/$tag; rm -rf $o; mkdir -p $o
-python bench.py --steps 20 --warmup 3 > $o/bench_unprofiled.json 2> $o/bench_unprofiled.err && echo "bench ok"
+python bench.py --steps 20 --warmup 3 --full > $o/bench_unprofiled.json 2> $o/bench_unprofiled.err && echo "bench ok"
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $o/bench.json 2> $o/bench.err && echo "stats ok"
 cp $(ls $o/stats/*/*kernel_stats.csv | head -1) $o/kernel_stats.csv
 python bench.py --steps 5 --warmup 2 --clips 6 --no-cpu-baseline --no-extras > $o/bench_n6.json 2> $o/bench_n6.err && echo "n6 ok"
