@@ -319,6 +319,37 @@ size_t vfr_bilstm_train_backward_workspace_bytes(int64_t B, int H);
 int vfr_bilstm_train_backward_f32(const float *gout, const float *gates, const float *cs, const float *WhhT_f, const float *WhhT_b,
                                   int64_t B, int T, int H, float *dpre, void *workspace, size_t workspace_bytes, vfr_stream_t stream);
 
+/* ---- f2  the training driver: Trainer.train_epoch's data path and optimizer step, model/main.py:43-80 ---------------
+ * triplet_gather  one batch of CustomBatchSampler triplets (model/data.py:249-343) -> custom_collate's tensors (:346-356) from
+ *                 the resident bank (seg [sum n, F], ctx [Nv, F], clip_off [Nv+1] int32) and token table tokens [A, Tq] int64.
+ *                 plan_host [S][7] int32 (HOST memory, read before return): video_pos, video_neg, start_t, end_t, start_tn,
+ *                 end_tn, token row.  Writes posit / inter [P, 2F+2] (rows (video_pos | video_neg, start_t..end_t)), intra
+ *                 [Nn, 2F+2] (video_pos, start_tn..end_tn), each row [seg[off[v] + t] | ctx[v] | t/n | (t+1)/n] (IEEE fp32
+ *                 division, make_visual_features :204-213); maskp [P], maskn [Nn] int64 = sample index; lang [S, Tq] int64.
+ *                 P and Nn must equal the plan's row totals; clip spans must be < 256.  One launch per 128 samples: the plan
+ *                 travels in the kernel arguments (no staging buffer to race on).  Outputs 8-byte aligned (rows are).
+ * adam_step       torch.optim.Adam(amsgrad=False, maximize=False) with L2 (not decoupled) weight decay over n <=
+ *                 VFR_ADAM_MAX_TENSORS fp32 tensors in ONE launch; host arrays of device pointers param / grad / exp_avg /
+ *                 exp_avg_sq, numel_host [n], coef_host [n][7] = fp32 {weight_decay, 1-beta1, beta2, 1-beta2, eps, -step_size,
+ *                 1/bias_correction2_sqrt} (the caller computes step_size and bias_correction2_sqrt in double from the step count,
+ *                 as torch does, and the reciprocal in fp32).  Per element, each op rounded: g' = g + wd p (wd != 0);
+ *                 m = lerp(m, g', 1-beta1); v = v beta2; v = v + (1-beta2) (g' g'); p = p + (-step_size) (m / (sqrt(v) *
+ *                 (1/bc2_sqrt) + eps)).  Also writes grad_sumsq[n] = sum of squares of every RAW gradient (before weight
+ *                 decay): fixed-order partials per 4096-element chunk, then a fixed-order reduce by the launch's last block
+ *                 (deterministic, no float atomics).  float4 where all four pointers of a tensor are 16-byte aligned.
+ * grad_sumsq      the same sums of squares without the update (utils.grad_norm's input for any optimizer).
+ * The workspace (vfr_adam_workspace_bytes, shared by both) must be ZERO before its first use; every call leaves it so.      */
+#define VFR_ADAM_MAX_TENSORS 32
+int vfr_triplet_gather_f32(const float *seg, const float *ctx, const int *clip_off, int num_videos, int F, const int64_t *tokens,
+                           int num_tokens_rows, int Tq, const int *plan_host, int S, int64_t P, int64_t Nn, float *posit,
+                           float *intra, float *inter, int64_t *maskp, int64_t *maskn, int64_t *lang, vfr_stream_t stream);
+size_t vfr_adam_workspace_bytes(const int64_t *numel_host, int n);
+int vfr_adam_step_f32(int n, float *const *param_host, const float *const *grad_host, float *const *exp_avg_host,
+                      float *const *exp_avg_sq_host, const int64_t *numel_host, const float *coef_host, float *grad_sumsq,
+                      void *workspace, size_t workspace_bytes, vfr_stream_t stream);
+int vfr_grad_sumsq_f32(int n, const float *const *grad_host, const int64_t *numel_host, float *grad_sumsq, void *workspace,
+                       size_t workspace_bytes, vfr_stream_t stream);
+
 /* ---- parity probe: elementwise canonical math (0 exp, 1 sigmoid, 2 tanh, 3 x/y, 4 sqrt,
  * 5 fma(x,y,x)) so tests can pin the device's transcendental forms against the oracle's.        */
 int vfr_math_f32(int op, const float *x, const float *y, float *out, int64_t n, vfr_stream_t stream);

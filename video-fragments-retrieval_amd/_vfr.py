@@ -71,6 +71,11 @@ SIGNATURES = {
     "vfr_bilstm_train_forward_f32": (_i32, [_vp, _i64, _i32, _i32, _i32] + [_vp] * 8 + [_vp, _vp, _vp, _vp]),
     "vfr_bilstm_train_backward_workspace_bytes": (_sz, [_i64, _i32]),
     "vfr_bilstm_train_backward_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "vfr_triplet_gather_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp]),
+    "vfr_adam_workspace_bytes": (_sz, [_vp, _i32]),
+    "vfr_adam_step_f32": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vfr_grad_sumsq_f32": (_i32, [_i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vfr_frames_normalize_f32": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "vfr_conv3x3_relu_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "vfr_maxpool2_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
@@ -779,3 +784,113 @@ def ranking_loss_backward(posit, intra, inter, lang, maskp, maskn, n_samples: in
                                            posit.shape[1], lamb, eps, g.data_ptr(), ws.data_ptr(), *[o.data_ptr() for o in outs],
                                            _stream()), "vfr_ranking_loss_grad_f32")
     return outs
+
+
+# ------------------------------------------------------------------------------------------------
+# the training driver (csrc/optim.hip): triplet batches from the resident bank, the fused Adam step and gradient sums of squares
+ADAM_MAX_TENSORS = 32                      # include/vfr.h VFR_ADAM_MAX_TENSORS
+
+
+def triplet_gather(seg, ctx, clip_off, tokens, plan: np.ndarray):
+    """One batch of sampler triplets -> (posit, intra, inter, lang, maskp, maskn) on the device (``custom_collate``'s dict,
+    ``model/data.py:346-356``).  ``plan`` [S, 7] int32 host array: video_pos, video_neg, start_t, end_t, start_tn, end_tn,
+    token row.  Row counts are prefix sums of the spans, taken here on the host."""
+    seg = _dev(seg, torch.float32, "seg")
+    ctx = _dev(ctx, torch.float32, "ctx")
+    clip_off = _dev(clip_off, torch.int32, "clip_off")
+    tokens = _dev(tokens, torch.int64, "tokens")
+    if seg.dim() != 2 or ctx.dim() != 2 or seg.shape[1] != ctx.shape[1] or clip_off.numel() != ctx.shape[0] + 1 or tokens.dim() != 2:
+        raise RuntimeError("triplet_gather: expected seg [sum n, F], ctx [Nv, F], clip_off [Nv+1], tokens [A, Tq]")
+    plan = np.ascontiguousarray(plan, dtype=np.int32)
+    if plan.ndim != 2 or plan.shape[1] != 7:
+        raise RuntimeError("triplet_gather: plan must be [S, 7] int32")
+    S, F, Tq = plan.shape[0], seg.shape[1], tokens.shape[1]
+    P = int((plan[:, 3] - plan[:, 2] + 1).sum())
+    Nn = int((plan[:, 5] - plan[:, 4] + 1).sum())
+    dev = seg.device
+    posit = torch.empty((P, 2 * F + 2), dtype=torch.float32, device=dev)
+    inter = torch.empty((P, 2 * F + 2), dtype=torch.float32, device=dev)
+    intra = torch.empty((Nn, 2 * F + 2), dtype=torch.float32, device=dev)
+    maskp = torch.empty(P, dtype=torch.int64, device=dev)
+    maskn = torch.empty(Nn, dtype=torch.int64, device=dev)
+    lang = torch.empty((S, Tq), dtype=torch.int64, device=dev)
+    _check(lib().vfr_triplet_gather_f32(seg.data_ptr(), ctx.data_ptr(), clip_off.data_ptr(), ctx.shape[0], F, tokens.data_ptr(),
+                                        tokens.shape[0], Tq, plan.ctypes.data, S, P, Nn, posit.data_ptr(), intra.data_ptr(),
+                                        inter.data_ptr(), maskp.data_ptr(), maskn.data_ptr(), lang.data_ptr(), _stream()),
+           "vfr_triplet_gather_f32")
+    return posit, intra, inter, lang, maskp, maskn
+
+
+def _ptr_array(ts):
+    return (ctypes.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
+
+
+def _flat_f32(ts, name):
+    for t in ts:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name}: expected tensors on the ROCm device (no CPU fallback in the HIP path)")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name}: expected torch.float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name}: tensors must be contiguous (they are updated in place)")
+
+
+_ADAM_WS = {}                              # device -> zero-initialised workspace (every call leaves it zero again)
+
+
+def _adam_workspace(numel, device) -> torch.Tensor:
+    arr = (ctypes.c_int64 * len(numel))(*numel)
+    need = int(lib().vfr_adam_workspace_bytes(arr, len(numel)))
+    ws = _ADAM_WS.get(device)
+    if ws is None or ws.numel() < need:
+        ws = torch.zeros(max(need, 1 << 16), dtype=torch.uint8, device=device)
+        _ADAM_WS[device] = ws
+    return ws
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, coefs, sumsq: torch.Tensor | None = None) -> torch.Tensor:
+    """In-place fused Adam step over the given tensors (include/vfr.h vfr_adam_step_f32), one launch per
+    ``ADAM_MAX_TENSORS``; ``coefs`` [n][7] = (wd, 1-beta1, beta2, 1-beta2, eps, -step_size, 1/bc2_sqrt) as fp32.
+    -> sums of squares of the raw gradients [n] f32 on the device."""
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(coefs) == n):
+        raise RuntimeError("adam_step: params, grads, exp_avgs, exp_avg_sqs and coefs must have the same length")
+    for name, ts in (("params", params), ("grads", grads), ("exp_avgs", exp_avgs), ("exp_avg_sqs", exp_avg_sqs)):
+        _flat_f32(ts, f"adam_step: {name}")
+    for i in range(n):
+        if not (params[i].shape == grads[i].shape == exp_avgs[i].shape == exp_avg_sqs[i].shape):
+            raise RuntimeError(f"adam_step: tensor {i}: shapes differ")
+    if n == 0:
+        return torch.zeros(0, dtype=torch.float32)
+    dev = params[0].device
+    if sumsq is None:
+        sumsq = torch.empty(n, dtype=torch.float32, device=dev)
+    coefs = np.ascontiguousarray(coefs, dtype=np.float32).reshape(n, 7)
+    for a in range(0, n, ADAM_MAX_TENSORS):
+        b = min(n, a + ADAM_MAX_TENSORS)
+        numel = [t.numel() for t in params[a:b]]
+        ws = _adam_workspace(numel, dev)
+        _check(lib().vfr_adam_step_f32(b - a, _ptr_array(params[a:b]), _ptr_array(grads[a:b]), _ptr_array(exp_avgs[a:b]),
+                                       _ptr_array(exp_avg_sqs[a:b]), (ctypes.c_int64 * (b - a))(*numel),
+                                       coefs[a:b].ctypes.data, sumsq[a:].data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "vfr_adam_step_f32")
+    return sumsq
+
+
+def grad_sumsq(grads) -> torch.Tensor:
+    """Sums of squares of the given gradients [n] f32 on the device (include/vfr.h vfr_grad_sumsq_f32), one launch per
+    ``ADAM_MAX_TENSORS`` tensors; deterministic."""
+    grads = [g if g.is_contiguous() else g.contiguous() for g in grads]
+    _flat_f32(grads, "grad_sumsq")
+    n = len(grads)
+    if n == 0:
+        return torch.zeros(0, dtype=torch.float32)
+    dev = grads[0].device
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    for a in range(0, n, ADAM_MAX_TENSORS):
+        b = min(n, a + ADAM_MAX_TENSORS)
+        numel = [t.numel() for t in grads[a:b]]
+        ws = _adam_workspace(numel, dev)
+        _check(lib().vfr_grad_sumsq_f32(b - a, _ptr_array(grads[a:b]), (ctypes.c_int64 * (b - a))(*numel), out[a:].data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream()), "vfr_grad_sumsq_f32")
+    return out
