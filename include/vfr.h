@@ -184,6 +184,33 @@ int vfr_score_topk_mfma(const float *Q, int64_t Nq, const float *V, const int32_
  * re-scored exactly, pairs the (video, group) bitmap can mark = Nq * Nv}.                                             */
 int vfr_score_topk_mfma_stats(const void *workspace, int64_t Nq, int Nv, int total_clips, int k, int64_t *stats_host,
                               vfr_stream_t stream);
+/* ---- video-level retrieval: which VIDEOS match a query.  Keys as vfr_score_topk_f32 ((distance, global moment id) ascending).
+ * The best key of a video is the smallest key among its moments (its first moment in the moment ranking; the WHOLE triangle
+ * decides it: an fp32 mean of several clips can round below the video's smallest clip distance).
+ *   k > 0 : out_dist [Nq,k] / out_idx [Nq,k] = the k smallest best keys over the bank's videos, as (distance, global moment id of
+ *           the video's best moment), i.e. the moment ranking reduced to the first moment of each video; video order is therefore
+ *           (best distance, video index).  Padded with (+inf, -1) when the bank has fewer than k videos.  k = 0: counts only.
+ *   own_dist / own_idx / video_count_lt [Nq] (nullable, together): video_count_lt[q] (int64) += number of this bank's videos
+ *           whose best key sorts strictly before (own_dist[q], own_idx[q]) -- the 0-based video rank of the query's own video
+ *           when that pair is its best key.  ADDED, so shards chain like count_lt.
+ *   dtype VFR_MFMA_F32    D = 100 and <= 21 clips per video (banks of at least score_mfma_min videos): per-(query, video) bounds
+ *                         of the smallest clip distance from the fp32 MFMA GEMM form with a rigorous margin exclude or count
+ *                         almost every video; the rest get their whole triangle with the canonical chain.  BIT-IDENTICAL to
+ *                         VFR_SCORE_EXACT; other shapes take the exact path.  | VFR_MFMA_BANK_READY: as vfr_score_topk_mfma (the
+ *                         bank-side products sit at the same workspace offsets and are checked by the same device hash).
+ *   dtype VFR_SCORE_EXACT every video's triangle with the canonical chain (any shape).
+ * Other arguments and limits as vfr_score_topk_f32 (max_clips <= 64, k <= 448, id_base + total moments < 2^32).
+ * vfr_score_video_topk_stats (measurement hook, SYNCHRONISES the stream): what the last VFR_MFMA_F32 fast-path call on `workspace`
+ * (same Nq, Nv, total_clips) re-scored exactly: stats_host [Nq, 2] = {videos given a triangle, of them rank-undecided}. */
+#define VFR_SCORE_EXACT 2
+size_t vfr_score_video_topk_workspace_bytes(int64_t Nq, int Nv, int total_clips, int k);
+int vfr_score_video_topk_f32(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets,
+                             const int64_t *moment_offsets, int Nv, int total_clips, int min_clips, int max_clips,
+                             int D, float eps, int64_t id_base, int k, float *out_dist, int64_t *out_idx,
+                             const float *own_dist, const int64_t *own_idx, int64_t *video_count_lt,
+                             int dtype, void *workspace, size_t workspace_bytes, vfr_stream_t stream);
+int vfr_score_video_topk_stats(const void *workspace, int64_t Nq, int Nv, int total_clips, int64_t *stats_host,
+                               vfr_stream_t stream);
 /* Device self-check of the arithmetic model the pre-filter's margins and the MFMA GEMMs' bit-exactness assume: a
  * v_mfma_f32_16x16x4_f32 = four fp32 fmas, k ascending, on its accumulator (denormals kept).  A, B [16, K] device rows
  * (K % 4 == 0; make them adversarial: wide exponent range, cancellation, denormals): C = A B^T by the matrix pipe against an

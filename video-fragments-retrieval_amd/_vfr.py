@@ -51,6 +51,10 @@ SIGNATURES = {
     "vfr_score_topk_mfma": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _vp, _vp, _i32,
                                    _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "vfr_score_topk_mfma_stats": (_i32, [_vp, _i64, _i32, _i32, _i32, ctypes.POINTER(ctypes.c_int64), _vp]),
+    "vfr_score_video_topk_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "vfr_score_video_topk_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _vp, _vp,
+                                        _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "vfr_score_video_topk_stats": (_i32, [_vp, _i64, _i32, _i32, ctypes.POINTER(ctypes.c_int64), _vp]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "vfr_topk_pack_keys": (_i32, [_vp, _vp, _i64, _vp, _vp]),
@@ -456,6 +460,59 @@ def score_topk(Q: torch.Tensor, bank: VideoBank, k: int, rank_dist=None, rank_id
         if pre:
             workspace._vfr_bank = token
     return od, oi, count_lt
+
+
+VIDEO_EXACT = 2                            # include/vfr.h VFR_SCORE_EXACT
+
+
+def score_video_topk(Q: torch.Tensor, bank: VideoBank, k: int, own_dist=None, own_idx=None, count=None,
+                     mode: str | None = None, workspace: torch.Tensor | None = None, eps: float = 1e-6):
+    """Video-level retrieval (include/vfr.h vfr_score_video_topk_f32): the k best DISTINCT videos per query, each as
+    (distance, global moment id) of its best moment, in (distance, id) order, padded with (+inf, -1); and, with
+    ``own_dist`` / ``own_idx`` [Nq] (the best key of each query's own video), ``count`` [Nq] int64 += the number of this
+    bank's videos whose best key sorts before it (allocated zeroed when None).  ``mode``: "mfma" (MFMA bounds + exact
+    triangles where they cannot decide) or "exact"; None = DEFAULT_SCORE_MODE.  Both give the same bits.
+    Returns (dist [Nq,k] | None, idx [Nq,k] int64 | None, count | None)."""
+    mode = mode or DEFAULT_SCORE_MODE
+    if mode not in ("exact", "mfma"):
+        raise RuntimeError(f"score_video_topk: unsupported mode {mode!r} (exact, mfma)")
+    Q = _dev(Q, torch.float32, "Q")
+    if mode == "mfma" and not _mfma_mode_ok(Q.device):
+        mode = "exact"
+    Nq = Q.shape[0]
+    od = torch.empty((Nq, k), dtype=torch.float32, device=Q.device) if k > 0 else None
+    oi = torch.empty((Nq, k), dtype=torch.int64, device=Q.device) if k > 0 else None
+    if own_dist is not None:
+        own_dist = _dev(own_dist, torch.float32, "own_dist").reshape(Nq)
+        own_idx = _dev(own_idx, torch.int64, "own_idx").reshape(Nq)
+        if count is None:
+            count = torch.zeros((Nq,), dtype=torch.int64, device=Q.device)
+        count = _dev(count, torch.int64, "count")
+    dtype = VIDEO_EXACT if mode == "exact" else SCORE_MODES["mfma"]
+    nbytes = lib().vfr_score_video_topk_workspace_bytes(Nq, bank.num_videos, bank.total_clips, k)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=Q.device)
+    token = ("video",) + bank.prep_token(0, eps)
+    ready = dtype == 0 and getattr(workspace, "_vfr_bank", None) == token
+    workspace._vfr_bank = None
+    _check(lib().vfr_score_video_topk_f32(Q.data_ptr(), Nq, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.mom_off.data_ptr(),
+                                          bank.num_videos, bank.total_clips, bank.min_clips, bank.max_clips, bank.dim, eps,
+                                          bank.id_base, k, _ptr(od), _ptr(oi), _ptr(own_dist), _ptr(own_idx), _ptr(count),
+                                          dtype | (MFMA_BANK_READY if ready else 0), workspace.data_ptr(), nbytes, _stream()),
+           "vfr_score_video_topk_f32")
+    if dtype == 0 and bank.dim == 100 and bank.max_clips <= 21 and bank.num_videos >= max(1, get_option("score_mfma_min")):
+        workspace._vfr_bank = token          # the fast path ran: the bank-side products are in the workspace
+    return od, oi, count
+
+
+def score_video_topk_stats(workspace: torch.Tensor, Nq: int, bank: VideoBank) -> np.ndarray:
+    """[Nq, 2] int64 of the last ``mode="mfma"`` fast-path call on ``workspace``: videos given an exact triangle per query, and
+    how many of them were undecided rank counts (synchronises)."""
+    out = np.zeros((Nq, 2), np.int64)
+    _check(lib().vfr_score_video_topk_stats(workspace.data_ptr(), Nq, bank.num_videos, bank.total_clips,
+                                            out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _stream()),
+           "vfr_score_video_topk_stats")
+    return out
 
 
 def score_mfma_stats(workspace: torch.Tensor, Nq: int, bank: VideoBank, k: int) -> dict:

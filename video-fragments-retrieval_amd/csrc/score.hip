@@ -2545,3 +2545,6 @@ extern "C" int vfr_mfma_selfcheck(const float *A, const float *B, int K, int rev
     VFR_CHECK_LAUNCH("mfma_selfcheck_kernel");
     return VFR_OK;
 }
+
+// video-level retrieval: top-k distinct videos and video rank counts (reuses the pre-filter's bank-side pre-passes above)
+#include "video_topk.h"

@@ -50,6 +50,10 @@ class HipOps:
         return self.v.score_topk(Q, bank, k, rank_dist, rank_idx, count_lt=count_lt, workspace=workspace,
                                  thr_seed=thr_seed, mode=self.score_mode)
 
+    def score_video_topk(self, Q, bank, k, own_dist=None, own_idx=None, count=None, workspace=None):
+        return self.v.score_video_topk(Q, bank, k, own_dist, own_idx, count=count, workspace=workspace,
+                                       mode=None if self.score_mode == "bf16" else self.score_mode)
+
     def slice_bank(self, bank, counts, v0, v1):
         return self.v.slice_bank(bank, counts, v0, v1)
 
@@ -628,6 +632,71 @@ def corpus_topk(shard: CorpusShard, Q, k, ops=None, world=1, workspace=None):
     return od, oi
 
 
+def own_best_keys(shard: CorpusShard, Q, own_global, ops, world=1):
+    """[Nq] int64 key of each query's own video's best moment (min over ALL its moments of (score, global id)); KEY_INF on
+    the ranks that do not hold the video, MIN-reduced over the ranks when world > 1."""
+    own = np.asarray(own_global, np.int64)
+    Nq = len(own)
+    gt = gt_index(shard, own)
+    if gt.sel is not None and gt.Mloc > 0:
+        labels = torch.ones((1, int(gt.sel.numel()), gt.Mloc), dtype=torch.bool, device=shard.device)
+        keys = best_positive_keys(shard, Q, QueryGT(1, Nq, gt.sel, gt.own_local, labels, gt.base, gt.all_local, gt.Mloc), ops,
+                                  world, reduce=False)[0]
+    else:
+        keys = torch.full((Nq,), KEY_INF, dtype=torch.int64, device=shard.device)
+    dist = _group(world)
+    if dist is not None:
+        dist.all_reduce(keys, op=dist.ReduceOp.MIN)
+    return keys
+
+
+def corpus_video_topk(shard: CorpusShard, Q, k, own_global=None, ops=None, world=1, workspace=None):
+    """Video-level retrieval over the corpus: the k best DISTINCT videos per query, each with its best moment, and (with
+    ``own_global``, the query's own global video index) the 0-based video rank of the query's own video = the number of
+    videos whose best key sorts strictly before that video's best key.  A video never spans shards, so the per-shard
+    lists merge with the moment-key merge and the counts add.
+    Returns (dist [Nq,k], best-moment id [Nq,k] int64, video index [Nq,k] int64 (-1 = padding), ranks [Nq] int64 | None)."""
+    ops = ops or HipOps()
+    Nq = Q.shape[0]
+    own_d = own_i = None
+    if own_global is not None:
+        own_d, own_i = _unpack_key(own_best_keys(shard, Q, own_global, ops, world))
+        own_d, own_i = own_d.contiguous(), own_i.contiguous()
+    od, oi, cnt = ops.score_video_topk(Q, shard.bank, k, own_d, own_i, workspace=workspace)
+    dist = _group(world)
+    if dist is not None:
+        if k > 0:
+            od, oi = gather_merge_topk(od, oi, ops, world)
+        if cnt is not None:
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+    vid = None
+    if k > 0:
+        mom = torch.from_numpy(shard.mom_off_all).to(oi.device)
+        vid = torch.where(oi >= 0, torch.searchsorted(mom, oi.clamp(min=0), right=True) - 1, torch.full_like(oi, -1))
+    return od, oi, vid, cnt
+
+
+def video_results(ids, dist, names, counts_all, mom_off_all):
+    """Search results as rows: per query a list of (video name, start_t, end_t, distance) for the global moment ids ``ids``
+    [Nq, k] (``corpus_video_topk`` / ``corpus_topk``); start_t / end_t are the inclusive clip span of the moment
+    (``utils.generate_moments``), the unit of the annotations' times.  Padding (-1) is skipped."""
+    ids = np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids, np.int64)
+    dist = np.asarray(dist.cpu() if isinstance(dist, torch.Tensor) else dist, np.float32)
+    mom = np.asarray(mom_off_all, np.int64)
+    rows = []
+    for q in range(ids.shape[0]):
+        out = []
+        for j in range(ids.shape[1]):
+            m = int(ids[q, j])
+            if m < 0:
+                continue
+            v = int(np.searchsorted(mom, m, side="right") - 1)
+            s, e = generate_moments(int(counts_all[v]))[m - int(mom[v])]
+            out.append((names[v], int(s), int(e), float(dist[q, j])))
+        rows.append(out)
+    return rows
+
+
 SAMPLE_VIDEOS = 256      # corpus-wide size of the threshold sample (the single-GPU kernel samples the same number itself)
 
 
@@ -816,6 +885,30 @@ class TorchCpuOps:
             od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
             oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
         return od, oi, counts
+
+    def score_video_topk(self, Q, bank, k, own_dist=None, own_idx=None, count=None, workspace=None):
+        """Video-level retrieval from the dense scores: per video the smallest (score, id) key, then the k smallest of those
+        and the number of videos below the own key (same semantics as ``_vfr.score_video_topk``)."""
+        sc = self._dense(Q, bank)
+        Nq = Q.shape[0]
+        keys = _pack_key(sc, (bank.id_base + torch.arange(sc.shape[1]))[None, :].expand_as(sc))
+        n = torch.tensor(bank.counts, dtype=torch.int64)
+        m = n * (n + 1) // 2
+        best = [keys[:, int(a):int(b)].min(dim=1).values for a, b in zip(m.cumsum(0) - m, m.cumsum(0)) if b > a]
+        best = torch.stack(best, dim=1) if best else torch.zeros((Nq, 0), dtype=torch.int64)
+        if own_dist is not None:
+            own = _pack_key(own_dist.reshape(Nq), own_idx.reshape(Nq))
+            c = (best < own[:, None]).sum(dim=1)
+            count = c if count is None else count + c
+        od = oi = None
+        if k > 0:
+            srt = best.sort(dim=1).values[:, :k]
+            if srt.shape[1] < k:
+                srt = torch.cat([srt, torch.full((Nq, k - srt.shape[1]), KEY_INF, dtype=torch.int64)], dim=1)
+            od, oi = _unpack_key(srt)
+            od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
+            oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
+        return od, oi, count
 
     def topk_merge(self, part_dist, part_idx):
         G, Nq, k = part_dist.shape

@@ -184,3 +184,37 @@ def validate_epoch(model, video_iterator, lang_iterator, annotations, device, si
             pr["recall"][k] = [float(t) / float(rel) for t, rel in zip(tp, relevant)]
         out["pr_curve"] = pr
     return out
+
+
+def evaluate_videos(model, video_iterator, lang_iterator, annotations, device, atk=(1, 10, 100), rank=0, world=1,
+                    return_topk=0):
+    """Video retrieval (VR) metrics of the same iterators ``evaluate`` consumes: which VIDEOS match a query.
+
+    A video's best key is its smallest (score, global moment id) over all its moments; the 0-based video rank of a query
+    is the number of videos whose best key sorts before its own video's best key.  Returns ``{"video": {"R@1", "R@10",
+    "R@100", "MR"}}`` (``get_metrics``: R@k = mean(rank < k) x 100, MR = median 0-based rank, as ``evaluate``); with
+    ``return_topk`` = k also ``(dist, moment idx, video idx)`` [Nq, k] of the k best distinct videos per query (the
+    moment is each video's best one).  Labels, IoU and annotation times play no part (``annotations`` is accepted for the
+    shared signature)."""
+    was_training = model.training
+    model.eval()
+    ops = engine.ops_for(device)
+    drained = _drain_videos(video_iterator)
+    tokens, q_videos, annot_ids = _drain_queries(lang_iterator)
+    if not tokens:
+        embed_corpus(model, video_iterator, device, ops, rank, world, drained)
+        model.train(was_training)
+        out = {"video": get_metrics({k: [] for k in list(atk) + ["MR"]})}
+        return (out, (None, None, None)) if return_topk else out
+    shard, names, Q = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world)
+    video_index = {name: i for i, name in enumerate(names)}
+    own = np.asarray([video_index[v] for v in q_videos], np.int64)
+    dist, idx, vid, ranks = engine.corpus_video_topk(shard, Q, int(return_topk), own, ops, world)
+    ranks = ranks.cpu().numpy()
+    model.train(was_training)
+    rec = {k: (ranks < k).astype(int) for k in atk}
+    rec["MR"] = ranks
+    out = {"video": get_metrics(rec)}
+    if return_topk:
+        return out, (dist, idx, vid)
+    return out
