@@ -211,6 +211,28 @@ int vfr_score_video_topk_f32(const float *Q, int64_t Nq, const float *V, const i
                              int dtype, void *workspace, size_t workspace_bytes, vfr_stream_t stream);
 int vfr_score_video_topk_stats(const void *workspace, int64_t Nq, int Nv, int total_clips, int64_t *stats_host,
                                vfr_stream_t stream);
+/* ---- diversified moment retrieval: the k best MOMENTS, at most per_video per video and no two of a video overlapping more
+ * than nms_iou.  Keys, ids and scores as vfr_score_topk_f32 ((distance, global moment id) ascending).  Per query and video, the
+ * video's moments are taken in key order and accepted greedily: a moment is suppressed when its IoU (utils.get_iou on the
+ * inclusive clip spans, float64) with an already accepted moment of the same video is > nms_iou; at most per_video are
+ * accepted (0 = no cap, values >= k act as k).  nms_iou >= 1 suppresses nothing, nms_iou = 0 keeps disjoint spans only.
+ *   out_dist [Nq,k] / out_idx [Nq,k] = the k smallest accepted keys over the bank, padded with (+inf, -1).
+ *   per_video = 1 gives exactly vfr_score_video_topk_f32's (dist, idx); per_video in {0, >= k} with nms_iou >= 1 gives exactly
+ *   vfr_score_topk_f32's top-k.  Every listed moment belongs to one of the query's k best videos, and a video never spans
+ *   shards: per-shard lists merge with vfr_topk_merge_f32.
+ *   dtype VFR_MFMA_F32 (| VFR_MFMA_BANK_READY) or VFR_SCORE_EXACT, as vfr_score_video_topk_f32 (its launch sequence finds the
+ *   k best videos; the workspace front is the same, so BANK_READY and the device hash work alike); BIT-IDENTICAL outputs.
+ * Limits as vfr_score_video_topk_f32 (k <= 448, max_clips <= 64, id_base + total moments < 2^32), Nq * k < 2^31; per_video >= 0;
+ * nms_iou >= 0 and not NaN.  Bad arguments: VFR_EINVAL.
+ * vfr_nms_inter_table (host only, no GPU): min_inter[0..max_len] = for each union length u the smallest integer intersection
+ * with (double)inter / u > nms_iou (u + 1 when none; entry 0 is 1) -- the exact, integer form of the IoU test the kernels use. */
+size_t vfr_score_moment_nms_workspace_bytes(int64_t Nq, int Nv, int total_clips, int k, int per_video);
+int vfr_score_moment_nms_f32(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets,
+                             const int64_t *moment_offsets, int Nv, int total_clips, int min_clips, int max_clips,
+                             int D, float eps, int64_t id_base, int k, int per_video, double nms_iou,
+                             float *out_dist, int64_t *out_idx, int dtype, void *workspace, size_t workspace_bytes,
+                             vfr_stream_t stream);
+int vfr_nms_inter_table(double nms_iou, int max_len, int32_t *min_inter);
 /* Device self-check of the arithmetic model the pre-filter's margins and the MFMA GEMMs' bit-exactness assume: a
  * v_mfma_f32_16x16x4_f32 = four fp32 fmas, k ascending, on its accumulator (denormals kept).  A, B [16, K] device rows
  * (K % 4 == 0; make them adversarial: wide exponent range, cancellation, denormals): C = A B^T by the matrix pipe against an

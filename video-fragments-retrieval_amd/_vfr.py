@@ -55,6 +55,10 @@ SIGNATURES = {
     "vfr_score_video_topk_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _vp, _vp,
                                         _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "vfr_score_video_topk_stats": (_i32, [_vp, _i64, _i32, _i32, ctypes.POINTER(ctypes.c_int64), _vp]),
+    "vfr_score_moment_nms_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    "vfr_score_moment_nms_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _i32,
+                                        ctypes.c_double, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "vfr_nms_inter_table": (_i32, [ctypes.c_double, _i32, ctypes.POINTER(ctypes.c_int32)]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "vfr_topk_pack_keys": (_i32, [_vp, _vp, _i64, _vp, _vp]),
@@ -503,6 +507,49 @@ def score_video_topk(Q: torch.Tensor, bank: VideoBank, k: int, own_dist=None, ow
     if dtype == 0 and bank.dim == 100 and bank.max_clips <= 21 and bank.num_videos >= max(1, get_option("score_mfma_min")):
         workspace._vfr_bank = token          # the fast path ran: the bank-side products are in the workspace
     return od, oi, count
+
+
+def score_moment_nms(Q: torch.Tensor, bank: VideoBank, k: int, per_video: int = 0, nms_iou: float = 1.0,
+                     mode: str | None = None, workspace: torch.Tensor | None = None, eps: float = 1e-6):
+    """Diversified moment retrieval (include/vfr.h vfr_score_moment_nms_f32): the k best moments per query in (distance,
+    global id) order, where each video's moments are accepted greedily in that order, a moment whose IoU with an accepted
+    moment of its video is > ``nms_iou`` is suppressed, and at most ``per_video`` are accepted (0 = no cap).  Padded with
+    (+inf, -1).  ``per_video`` = 1 is ``score_video_topk``; no cap and ``nms_iou`` >= 1 is ``score_topk``.  ``mode``:
+    "mfma" or "exact" (same bits); None = DEFAULT_SCORE_MODE.  Returns (dist [Nq,k], idx [Nq,k] int64)."""
+    mode = mode or DEFAULT_SCORE_MODE
+    if mode not in ("exact", "mfma"):
+        raise RuntimeError(f"score_moment_nms: unsupported mode {mode!r} (exact, mfma)")
+    Q = _dev(Q, torch.float32, "Q")
+    if mode == "mfma" and not _mfma_mode_ok(Q.device):
+        mode = "exact"
+    Nq = Q.shape[0]
+    od = torch.empty((Nq, k), dtype=torch.float32, device=Q.device)
+    oi = torch.empty((Nq, k), dtype=torch.int64, device=Q.device)
+    dtype = VIDEO_EXACT if mode == "exact" else SCORE_MODES["mfma"]
+    nbytes = lib().vfr_score_moment_nms_workspace_bytes(Nq, bank.num_videos, bank.total_clips, k, int(per_video))
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=Q.device)
+    token = ("video",) + bank.prep_token(0, eps)        # the workspace front is score_video_topk's
+    ready = dtype == 0 and getattr(workspace, "_vfr_bank", None) == token
+    workspace._vfr_bank = None
+    _check(lib().vfr_score_moment_nms_f32(Q.data_ptr(), Nq, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.mom_off.data_ptr(),
+                                          bank.num_videos, bank.total_clips, bank.min_clips, bank.max_clips, bank.dim, eps,
+                                          bank.id_base, k, int(per_video), float(nms_iou), _ptr(od), _ptr(oi),
+                                          dtype | (MFMA_BANK_READY if ready else 0), workspace.data_ptr(), nbytes, _stream()),
+           "vfr_score_moment_nms_f32")
+    if k > 0 and Nq > 0 and dtype == 0 and bank.dim == 100 and bank.max_clips <= 21 and \
+            bank.num_videos >= max(1, get_option("score_mfma_min")):
+        workspace._vfr_bank = token          # the fast path ran: the bank-side products are in the workspace
+    return od, oi
+
+
+def nms_inter_table(nms_iou: float, max_len: int = 64) -> np.ndarray:
+    """[max_len + 1] int32: per union length u the smallest integer intersection with inter / u > nms_iou in float64 (u + 1
+    when none) -- the exact form of the IoU test of ``score_moment_nms`` (no GPU needed)."""
+    out = np.zeros(max_len + 1, np.int32)
+    _check(lib().vfr_nms_inter_table(float(nms_iou), int(max_len), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+           "vfr_nms_inter_table")
+    return out
 
 
 def score_video_topk_stats(workspace: torch.Tensor, Nq: int, bank: VideoBank) -> np.ndarray:

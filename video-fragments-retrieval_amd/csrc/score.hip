@@ -2548,3 +2548,6 @@ extern "C" int vfr_mfma_selfcheck(const float *A, const float *B, int K, int rev
 
 // video-level retrieval: top-k distinct videos and video rank counts (reuses the pre-filter's bank-side pre-passes above)
 #include "video_topk.h"
+
+// diversified moment retrieval: per-video cap and temporal NMS over the video top-k above
+#include "moment_nms.h"

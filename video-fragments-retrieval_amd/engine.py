@@ -54,6 +54,10 @@ class HipOps:
         return self.v.score_video_topk(Q, bank, k, own_dist, own_idx, count=count, workspace=workspace,
                                        mode=None if self.score_mode == "bf16" else self.score_mode)
 
+    def score_moment_nms(self, Q, bank, k, per_video=0, nms_iou=1.0, workspace=None):
+        return self.v.score_moment_nms(Q, bank, k, per_video, nms_iou, workspace=workspace,
+                                       mode=None if self.score_mode == "bf16" else self.score_mode)
+
     def slice_bank(self, bank, counts, v0, v1):
         return self.v.slice_bank(bank, counts, v0, v1)
 
@@ -669,11 +673,27 @@ def corpus_video_topk(shard: CorpusShard, Q, k, own_global=None, ops=None, world
             od, oi = gather_merge_topk(od, oi, ops, world)
         if cnt is not None:
             dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
-    vid = None
-    if k > 0:
-        mom = torch.from_numpy(shard.mom_off_all).to(oi.device)
-        vid = torch.where(oi >= 0, torch.searchsorted(mom, oi.clamp(min=0), right=True) - 1, torch.full_like(oi, -1))
+    vid = _video_of(shard, oi) if k > 0 else None
     return od, oi, vid, cnt
+
+
+def _video_of(shard: CorpusShard, oi):
+    """[Nq, k] global video index of global moment ids (-1 stays -1)."""
+    mom = torch.from_numpy(shard.mom_off_all).to(oi.device)
+    return torch.where(oi >= 0, torch.searchsorted(mom, oi.clamp(min=0), right=True) - 1, torch.full_like(oi, -1))
+
+
+def corpus_moment_nms(shard: CorpusShard, Q, k, per_video=0, nms_iou=1.0, ops=None, world=1, workspace=None):
+    """Diversified moment retrieval over the corpus: the k best moments per query where each video's moments are accepted
+    greedily in (distance, global id) order, a moment whose IoU with an accepted moment of its video is > ``nms_iou`` is
+    suppressed (``utils.get_iou``, float64) and at most ``per_video`` moments are accepted (0 = no cap).  NMS never crosses
+    a video and a video never spans shards, so the per-shard lists merge with the moment-key merge.
+    Returns (dist [Nq,k], moment id [Nq,k] int64, video index [Nq,k] int64 (-1 = padding)); the ids feed ``video_results``."""
+    ops = ops or HipOps()
+    od, oi = ops.score_moment_nms(Q, shard.bank, k, per_video, nms_iou, workspace=workspace)
+    if k > 0 and _group(world) is not None:
+        od, oi = gather_merge_topk(od, oi, ops, world)
+    return od, oi, _video_of(shard, oi)
 
 
 def video_results(ids, dist, names, counts_all, mom_off_all):
@@ -909,6 +929,44 @@ class TorchCpuOps:
             od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
             oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
         return od, oi, count
+
+    def score_moment_nms(self, Q, bank, k, per_video=0, nms_iou=1.0, workspace=None):
+        """Diversified moment retrieval from the dense scores (same rule as ``_vfr.score_moment_nms``): per video, moments in
+        key order, greedy acceptance under the float64 IoU test and the cap, then the k smallest accepted keys."""
+        sc = self._dense(Q, bank)
+        Nq = Q.shape[0]
+        keys = _pack_key(sc, (bank.id_base + torch.arange(sc.shape[1]))[None, :].expand_as(sc))
+        acc = torch.full_like(keys, KEY_INF)
+        cap = per_video if per_video > 0 else sc.shape[1] + 1
+        m0 = 0
+        for n in bank.counts:
+            spans = np.asarray(generate_moments(int(n)), np.int64).reshape(-1, 2)
+            M = len(spans)
+            if M == 0:
+                continue
+            s, e = spans[:, 0], spans[:, 1]
+            inter = np.maximum(np.minimum(e[:, None], e[None, :]) + 1 - np.maximum(s[:, None], s[None, :]), 0)
+            union = np.maximum(e[:, None], e[None, :]) + 1 - np.minimum(s[:, None], s[None, :])
+            supp = torch.from_numpy(inter / union > nms_iou) | torch.eye(M, dtype=torch.bool)
+            kv = keys[:, m0:m0 + M]
+            order = kv.argsort(dim=1)
+            alive = torch.ones((Nq, M), dtype=torch.bool)
+            taken = torch.zeros((Nq,), dtype=torch.int64)
+            rows = torch.arange(Nq)
+            for r in range(M):
+                j = order[:, r]
+                take = alive[rows, j] & (taken < cap)
+                alive &= ~(supp[j] & take[:, None])
+                taken += take.long()
+                acc[rows[take], m0 + j[take]] = kv[rows[take], j[take]]
+            m0 += M
+        srt = acc.sort(dim=1).values[:, :k]
+        if srt.shape[1] < k:
+            srt = torch.cat([srt, torch.full((Nq, k - srt.shape[1]), KEY_INF, dtype=torch.int64)], dim=1)
+        od, oi = _unpack_key(srt)
+        od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
+        oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
+        return od, oi
 
     def topk_merge(self, part_dist, part_idx):
         G, Nq, k = part_dist.shape

@@ -218,3 +218,48 @@ def evaluate_videos(model, video_iterator, lang_iterator, annotations, device, a
     if return_topk:
         return out, (dist, idx, vid)
     return out
+
+
+def evaluate_moments_nms(model, video_iterator, lang_iterator, annotations, device, per_video=0, nms_iou=0.5,
+                         atk=(1, 10, 100), iou_thresholds=(0.5, 0.7), rank=0, world=1, return_topk=False):
+    """Moment retrieval metrics over a DIVERSIFIED list (``engine.corpus_moment_nms``): per video, moments are accepted in
+    (score, global id) order unless their IoU with an accepted moment of the same video is > ``nms_iou``, at most
+    ``per_video`` of them (0 = no cap); the list is the max(atk) best accepted moments.
+
+    A query is a hit at k for threshold thr when one of its first k results is a positive moment: in the query's own video
+    and with ``(get_iou(times, s, e) > thr).sum() >= 2`` -- the strict label table ``evaluate`` builds (reference
+    ``evaluate.py:62``).  Returns ``{"model, IoU=<thr>": {"R@1", "R@10", "R@100"}}`` (``get_metrics``; no MR: a rank inside
+    the diversified list is not defined here); with ``return_topk`` also ``(dist, moment idx, video idx)`` [Nq, max(atk)].
+    With ``per_video`` = 0 and ``nms_iou`` >= 1 the list is the plain moment ranking and R@k equals ``evaluate``'s."""
+    was_training = model.training
+    model.eval()
+    ops = engine.ops_for(device)
+    drained = _drain_videos(video_iterator)
+    tokens, q_videos, annot_ids = _drain_queries(lang_iterator)
+    K = max(atk)
+    if not tokens:
+        embed_corpus(model, video_iterator, device, ops, rank, world, drained)
+        model.train(was_training)
+        out = {f"model, IoU={thr}": get_metrics({k: [] for k in atk}) for thr in iou_thresholds}
+        return (out, (None, None, None)) if return_topk else out
+    shard, names, Q = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world)
+    video_index = {name: i for i, name in enumerate(names)}
+    own = np.asarray([video_index[v] for v in q_videos], np.int64)
+    times = [annotations[a]["times"] for a in annot_ids]
+    labels = engine.gt_labels(times, shard.counts_all[own], list(iou_thresholds), True, shard.device, ops)
+    dist, idx, vid = engine.corpus_moment_nms(shard, Q, K, per_video, nms_iou, ops, world)
+    model.train(was_training)
+    lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+    ids, vids = idx.cpu().numpy(), vid.cpu().numpy()
+    local = ids - np.asarray(shard.mom_off_all, np.int64)[own][:, None]
+    mine = (vids == own[:, None]) & (ids >= 0)
+    local = np.where(mine, local, 0)
+    rows = np.arange(len(own))[:, None]
+    out = {}
+    for r, thr in enumerate(iou_thresholds):
+        pos = mine & lab[r][rows, local].astype(bool)
+        first = np.where(pos.any(axis=1), pos.argmax(axis=1), K)          # position of the first positive result
+        out[f"model, IoU={thr}"] = get_metrics({k: (first < k).astype(int) for k in atk})
+    if return_topk:
+        return out, (dist, idx, vid)
+    return out
