@@ -233,6 +233,34 @@ int vfr_score_moment_nms_f32(const float *Q, int64_t Nq, const float *V, const i
                              float *out_dist, int64_t *out_idx, int dtype, void *workspace, size_t workspace_bytes,
                              vfr_stream_t stream);
 int vfr_nms_inter_table(double nms_iou, int max_len, int32_t *min_inter);
+/* ---- candidate-restricted retrieval: search only the videos each query lists ("these videos": a per-user library or a metadata
+ * filter, a first-stage shortlist, the candidate-pool evaluation protocol).  Keys, ids and scores as vfr_score_topk_f32.
+ * cand_off [Nq+1] int64 / cand_vid [nnz] int32: CSR lists of CORPUS-GLOBAL video indices, strictly ascending per query;
+ * vid_base = global index of the bank's first video: entries outside [vid_base, vid_base + Nv) are skipped, so every shard takes
+ * the same lists (a video never spans shards).  max_list (host) = the longest list: it sizes the grid without a synchronisation.
+ *   level VFR_SUBSET_MOMENTS: out_dist / out_idx [Nq,k] = the k smallest keys over all moments of the query's listed videos of this
+ *           bank, padded with (+inf, -1); count_lt[r][q] += number of those moments whose key sorts strictly before
+ *           (rank_dist[r][q], rank_idx[r][q]), as vfr_score_topk_f32 counts.
+ *   level VFR_SUBSET_VIDEOS: out_* = the k smallest BEST keys of the listed videos, as (best distance, id of the best moment);
+ *           count_lt[r][q] += number of listed videos whose best key sorts strictly before the rank key, as video_count_lt.
+ *   Every list = every video of the bank gives exactly vfr_score_topk_f32 (moments) and vfr_score_video_topk_f32 (videos).
+ * num_rank <= 4 ([num_rank, Nq] rank_dist / rank_idx / count_lt, ADDED); k = 0 with counts only is allowed.  An empty list gives
+ * padding and adds nothing.  Cost scales with the listed (query, video) pairs, not with Nq x Nv; the result is exact (the
+ * canonical chain and the whole triangle of every listed video).
+ * bad (nullable, device int): set to 1 when a list is not strictly ascending, holds an index < 0, is longer than max_list, or
+ * cand_off is not a non-decreasing run from 0 to nnz (results for such lists are unspecified; nothing is read or written out of
+ * bounds).  Limits as vfr_score_video_topk_f32 (k <= 448, max_clips <= 64, id_base + total moments < 2^32), Nq * k < 2^31,
+ * nnz < 2^31.  Bad host-side arguments: VFR_EINVAL before anything is enqueued.
+ * vfr_score_subset_workspace_bytes: O((nnz / 64 + Nq) k) for moments, O(nnz) for videos (0 for a bad argument).        */
+#define VFR_SUBSET_MOMENTS 0
+#define VFR_SUBSET_VIDEOS 1
+size_t vfr_score_subset_workspace_bytes(int64_t Nq, int64_t nnz, int64_t max_list, int k, int level);
+int vfr_score_subset_f32(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets,
+                         const int64_t *moment_offsets, int Nv, int total_clips, int min_clips, int max_clips, int D,
+                         float eps, int64_t id_base, int64_t vid_base, const int64_t *cand_off, const int32_t *cand_vid,
+                         int64_t nnz, int64_t max_list, int level, int k, float *out_dist, int64_t *out_idx, int num_rank,
+                         const float *rank_dist, const int64_t *rank_idx, int64_t *count_lt, int *bad, void *workspace,
+                         size_t workspace_bytes, vfr_stream_t stream);
 /* Device self-check of the arithmetic model the pre-filter's margins and the MFMA GEMMs' bit-exactness assume: a
  * v_mfma_f32_16x16x4_f32 = four fp32 fmas, k ascending, on its accumulator (denormals kept).  A, B [16, K] device rows
  * (K % 4 == 0; make them adversarial: wide exponent range, cancellation, denormals): C = A B^T by the matrix pipe against an

@@ -59,6 +59,9 @@ SIGNATURES = {
     "vfr_score_moment_nms_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _i32,
                                         ctypes.c_double, _vp, _vp, _i32, _vp, _sz, _vp]),
     "vfr_nms_inter_table": (_i32, [ctypes.c_double, _i32, ctypes.POINTER(ctypes.c_int32)]),
+    "vfr_score_subset_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32]),
+    "vfr_score_subset_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i64, _vp, _vp, _i64, _i64,
+                                    _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "vfr_topk_pack_keys": (_i32, [_vp, _vp, _i64, _vp, _vp]),
@@ -541,6 +544,55 @@ def score_moment_nms(Q: torch.Tensor, bank: VideoBank, k: int, per_video: int = 
             bank.num_videos >= max(1, get_option("score_mfma_min")):
         workspace._vfr_bank = token          # the fast path ran: the bank-side products are in the workspace
     return od, oi
+
+
+SUBSET_LEVELS = {"moments": 0, "videos": 1}   # include/vfr.h VFR_SUBSET_MOMENTS / VFR_SUBSET_VIDEOS
+
+
+def score_subset(Q: torch.Tensor, bank: VideoBank, cand_off: torch.Tensor, cand_vid: torch.Tensor, k: int, level: str = "moments",
+                 vid_base: int = 0, rank_dist=None, rank_idx=None, count_lt=None, workspace: torch.Tensor | None = None,
+                 bad: torch.Tensor | None = None, max_list: int | None = None, eps: float = 1e-6):
+    """Candidate-restricted retrieval (include/vfr.h vfr_score_subset_f32): each query searches only the videos its list names.
+    ``cand_off`` [Nq+1] int64 / ``cand_vid`` [nnz] int32 = CSR lists of corpus-global video indices, strictly ascending per query;
+    ``vid_base`` = global index of the bank's first video (entries of other shards are skipped).  ``level`` "moments": the k best
+    moments of the listed videos; "videos": the k best listed videos as (best distance, best moment id).  Padded with (+inf, -1).
+    rank_dist / rank_idx [R, Nq] (or [Nq]), R <= 4: ``count_lt`` [R, Nq] int64 += the moments (videos) of the lists that sort
+    before each rank key (allocated zeroed when None).  ``bad`` (device int32 [1], nullable) is set to 1 for a malformed list.
+    ``max_list`` = the longest list (read from ``cand_off`` -- one synchronisation -- when None).
+    Returns (dist [Nq,k] | None, idx [Nq,k] int64 | None, count_lt | None)."""
+    if level not in SUBSET_LEVELS:
+        raise RuntimeError(f"score_subset: unknown level {level!r} (moments, videos)")
+    Q = _dev(Q, torch.float32, "Q")
+    Nq = Q.shape[0]
+    cand_off = _dev(cand_off, torch.int64, "cand_off")
+    cand_vid = _dev(cand_vid, torch.int32, "cand_vid")
+    if cand_off.numel() != Nq + 1:
+        raise RuntimeError(f"score_subset: cand_off has {cand_off.numel()} entries, expected Nq + 1 = {Nq + 1}")
+    nnz = int(cand_vid.numel())
+    if max_list is None:
+        max_list = int((cand_off[1:] - cand_off[:-1]).max()) if Nq > 0 else 0
+    od = torch.empty((Nq, k), dtype=torch.float32, device=Q.device) if k > 0 else None
+    oi = torch.empty((Nq, k), dtype=torch.int64, device=Q.device) if k > 0 else None
+    R = 0
+    if rank_dist is not None:
+        rank_dist = _dev(rank_dist, torch.float32, "rank_dist").reshape(-1, Nq)
+        rank_idx = _dev(rank_idx, torch.int64, "rank_idx").reshape(-1, Nq)
+        R = rank_dist.shape[0]
+        if count_lt is None:
+            count_lt = torch.zeros((R, Nq), dtype=torch.int64, device=Q.device)
+        count_lt = _dev(count_lt, torch.int64, "count_lt")
+    if bad is not None:
+        bad = _dev(bad, torch.int32, "bad")
+    lv = SUBSET_LEVELS[level]
+    nbytes = lib().vfr_score_subset_workspace_bytes(Nq, nnz, int(max_list), k, lv)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=Q.device)
+    _check(lib().vfr_score_subset_f32(Q.data_ptr(), Nq, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.mom_off.data_ptr(),
+                                      bank.num_videos, bank.total_clips, bank.min_clips, bank.max_clips, bank.dim, eps, bank.id_base,
+                                      int(vid_base), cand_off.data_ptr(), _ptr(cand_vid) if nnz else 0, nnz, int(max_list), lv, k,
+                                      _ptr(od), _ptr(oi), R, _ptr(rank_dist), _ptr(rank_idx), _ptr(count_lt), _ptr(bad),
+                                      workspace.data_ptr(), nbytes, _stream()), "vfr_score_subset_f32")
+    return od, oi, count_lt
 
 
 def nms_inter_table(nms_iou: float, max_len: int = 64) -> np.ndarray:

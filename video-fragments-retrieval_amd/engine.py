@@ -58,6 +58,11 @@ class HipOps:
         return self.v.score_moment_nms(Q, bank, k, per_video, nms_iou, workspace=workspace,
                                        mode=None if self.score_mode == "bf16" else self.score_mode)
 
+    def score_subset(self, Q, bank, cand_off, cand_vid, k, level="moments", vid_base=0, rank_dist=None, rank_idx=None, count_lt=None,
+                     workspace=None, bad=None, max_list=None):
+        return self.v.score_subset(Q, bank, cand_off, cand_vid, k, level, vid_base, rank_dist, rank_idx, count_lt=count_lt,
+                                   workspace=workspace, bad=bad, max_list=max_list)
+
     def slice_bank(self, bank, counts, v0, v1):
         return self.v.slice_bank(bank, counts, v0, v1)
 
@@ -696,6 +701,99 @@ def corpus_moment_nms(shard: CorpusShard, Q, k, per_video=0, nms_iou=1.0, ops=No
     return od, oi, _video_of(shard, oi)
 
 
+@dataclass
+class CandidateLists:
+    """Per-query candidate videos as CSR (``candidate_lists``): ``off`` [Nq+1] int64 and ``vid`` [nnz] int32 corpus-global video
+    indices, sorted and de-duplicated per query, on the host; ``max_list`` = the longest list.  ``on(device)`` uploads them once."""
+    off: np.ndarray
+    vid: np.ndarray
+    max_list: int
+    _dev: dict = None
+
+    @property
+    def num_queries(self):
+        return len(self.off) - 1
+
+    def on(self, device):
+        device = torch.device(device)
+        if self._dev is None:
+            self._dev = {}
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.off).to(device), torch.from_numpy(self.vid).to(device))
+        return self._dev[key]
+
+
+def candidate_lists(pools, names=None, num_videos=None, device=None) -> CandidateLists:
+    """CSR candidate lists from per-query iterables of video names (looked up in ``names``, the corpus order) or global video
+    indices (0 <= i < ``num_videos``, default len(names)); each list is sorted and de-duplicated.  Unknown names and indices out
+    of range raise ValueError.  ``device``: upload the CSR there as well (``CandidateLists.on``)."""
+    index = {n: i for i, n in enumerate(names)} if names is not None else None
+    if num_videos is None and names is not None:
+        num_videos = len(names)
+    rows = []
+    for q, pool in enumerate(pools):
+        ids = []
+        for x in pool:
+            if isinstance(x, (int, np.integer)) and not isinstance(x, bool):
+                i = int(x)
+                if i < 0 or (num_videos is not None and i >= num_videos):
+                    raise ValueError(f"candidate_lists: query {q}: video index {i} out of range [0, {num_videos})")
+            else:
+                if index is None:
+                    raise ValueError(f"candidate_lists: query {q}: video name {x!r} given without `names`")
+                i = index.get(x)
+                if i is None:
+                    raise ValueError(f"candidate_lists: query {q}: unknown video {x!r}")
+            ids.append(i)
+        rows.append(np.unique(np.asarray(ids, np.int64)))
+    lens = np.asarray([len(r) for r in rows], np.int64)
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    vid = (np.concatenate(rows) if rows else np.zeros(0, np.int64)).astype(np.int32)
+    out = CandidateLists(off, vid, int(lens.max()) if len(lens) else 0)
+    if device is not None:
+        out.on(device)
+    return out
+
+
+def corpus_subset_topk(shard: CorpusShard, Q, k, lists: CandidateLists, level="moments", own_global=None, ops=None, world=1,
+                       workspace=None, rank_keys=None):
+    """Candidate-restricted retrieval: each query searches only the videos of its list (``candidate_lists``).  ``level``
+    "moments": the k best moments of the listed videos; "videos": the k best listed videos, each as its best moment.  Every rank
+    passes the same lists with its first video as ``vid_base``; a video never spans shards, so the lists merge with the
+    moment-key merge and the counts add.
+    Counts: ``rank_keys`` [R, Nq] packed keys -> [R, Nq] = the listed moments (videos) that sort before each key; else
+    ``own_global`` -> [Nq] = the 0-based rank of the query's own video's best key among the listed moments (videos).
+    Returns (dist [Nq,k], moment id [Nq,k] int64, video index [Nq,k] int64 (-1 = padding), counts | None); the ids feed
+    ``video_results``."""
+    ops = ops or HipOps()
+    if level not in ("moments", "videos"):
+        raise ValueError(f"corpus_subset_topk: unknown level {level!r} (moments, videos)")
+    if lists.num_queries != Q.shape[0]:
+        raise ValueError(f"corpus_subset_topk: {lists.num_queries} lists for {Q.shape[0]} queries")
+    squeeze = False
+    rd = ri = None
+    if rank_keys is None and own_global is not None:
+        rank_keys = own_best_keys(shard, Q, own_global, ops, world)[None]
+        squeeze = True
+    if rank_keys is not None:
+        rd, ri = _unpack_key(rank_keys)
+        rd, ri = rd.contiguous(), ri.contiguous()
+    off_t, vid_t = lists.on(shard.device)
+    od, oi, cnt = ops.score_subset(Q, shard.bank, off_t, vid_t, k, level, shard.lo, rd, ri, workspace=workspace,
+                                   max_list=lists.max_list)
+    dist = _group(world)
+    if dist is not None:
+        if k > 0:
+            od, oi = gather_merge_topk(od, oi, ops, world)
+        if cnt is not None:
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+    vid = _video_of(shard, oi) if k > 0 else None
+    if cnt is not None and squeeze:
+        cnt = cnt[0]
+    return od, oi, vid, cnt
+
+
 def video_results(ids, dist, names, counts_all, mom_off_all):
     """Search results as rows: per query a list of (video name, start_t, end_t, distance) for the global moment ids ``ids``
     [Nq, k] (``corpus_video_topk`` / ``corpus_topk``); start_t / end_t are the inclusive clip span of the moment
@@ -967,6 +1065,49 @@ class TorchCpuOps:
         od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
         oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
         return od, oi
+
+    def score_subset(self, Q, bank, cand_off, cand_vid, k, level="moments", vid_base=0, rank_dist=None, rank_idx=None, count_lt=None,
+                     workspace=None, bad=None, max_list=None):
+        """Candidate-restricted retrieval from the dense scores (same semantics as ``_vfr.score_subset``): per query the keys of
+        the listed videos of this bank (moments, or each video's smallest key), the k smallest, and the keys below each rank key."""
+        if level not in ("moments", "videos"):
+            raise RuntimeError(f"score_subset: unknown level {level!r} (moments, videos)")
+        sc = self._dense(Q, bank)
+        Nq = Q.shape[0]
+        keys = _pack_key(sc, (bank.id_base + torch.arange(sc.shape[1]))[None, :].expand_as(sc))
+        n = np.asarray(bank.counts, np.int64)
+        Nv = len(n)
+        mo = np.concatenate([[0], np.cumsum(n * (n + 1) // 2)]).astype(np.int64)
+        off = [int(x) for x in torch.as_tensor(cand_off).tolist()]
+        vid = [int(x) for x in torch.as_tensor(cand_vid).tolist()]
+        kstar = None
+        if rank_dist is not None:
+            kstar = _pack_key(rank_dist.reshape(-1, Nq).contiguous(), rank_idx.reshape(-1, Nq))
+        R = 0 if kstar is None else kstar.shape[0]
+        counts = torch.zeros((R, Nq), dtype=torch.int64)
+        rows = []
+        for q in range(Nq):
+            sel = [v - vid_base for v in vid[off[q]:off[q + 1]] if 0 <= v - vid_base < Nv and n[v - vid_base] > 0]
+            if level == "moments":
+                cols = np.concatenate([np.arange(mo[v], mo[v + 1]) for v in sel]) if sel else np.zeros(0, np.int64)
+                kk = keys[q, torch.from_numpy(cols)]
+            else:
+                kk = torch.stack([keys[q, int(mo[v]):int(mo[v + 1])].min() for v in sel]) if sel else torch.zeros(0, dtype=torch.int64)
+            if R:
+                counts[:, q] = (kk[None, :] < kstar[:, q, None]).sum(dim=1)
+            srt = kk.sort().values[:k]
+            rows.append(torch.cat([srt, torch.full((k - srt.numel(),), KEY_INF, dtype=torch.int64)]))
+        od = oi = None
+        if k > 0:
+            srt = torch.stack(rows) if rows else torch.zeros((0, k), dtype=torch.int64)
+            od, oi = _unpack_key(srt)
+            od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
+            oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
+        if R == 0:
+            counts = None
+        elif count_lt is not None:
+            counts = counts + count_lt
+        return od, oi, counts
 
     def topk_merge(self, part_dist, part_idx):
         G, Nq, k = part_dist.shape

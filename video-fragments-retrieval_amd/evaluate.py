@@ -263,3 +263,63 @@ def evaluate_moments_nms(model, video_iterator, lang_iterator, annotations, devi
     if return_topk:
         return out, (dist, idx, vid)
     return out
+
+
+def evaluate_candidates(model, video_iterator, lang_iterator, annotations, device, pools, level="moments", atk=(1, 10, 100),
+                        iou_thresholds=(0.5, 0.7), rank=0, world=1, return_topk=0):
+    """Retrieval metrics among per-query CANDIDATE POOLS (``engine.corpus_subset_topk``): each query is ranked only against the
+    videos of its pool -- a per-user library, a first-stage shortlist, or the usual protocol of the query's own video plus N
+    distractors.  ``pools``: one iterable of video names or global video indices per query, in ``lang_iterator`` order.  The
+    query's own video is ALWAYS added to its pool (a pool without it would leave the rank undefined).
+
+    ``level`` "moments": per IoU threshold, the 0-based rank of the best ground-truth-positive moment (the strict labels and the
+    best-positive keys of ``evaluate``) among all moments of the pool -> ``{"model, IoU=<thr>": {"R@1", "R@10", "R@100", "MR"}}``;
+    a query without a positive moment raises IndexError as in ``evaluate``.  ``level`` "videos": the 0-based rank of the own video's
+    best key among the pool's videos -> ``{"video": {...}}`` as ``evaluate_videos``.  With every pool = all videos the dicts equal
+    ``evaluate``'s "model" entries and ``evaluate_videos``.  ``return_topk`` = k also returns ``(dist, moment idx, video idx)``
+    [Nq, k] of the pool's k best moments (videos)."""
+    if level not in ("moments", "videos"):
+        raise ValueError(f"evaluate_candidates: unknown level {level!r} (moments, videos)")
+    was_training = model.training
+    model.eval()
+    ops = engine.ops_for(device)
+    drained = _drain_videos(video_iterator)
+    tokens, q_videos, annot_ids = _drain_queries(lang_iterator)
+    if not tokens:
+        empty = ({"video": get_metrics({k: [] for k in list(atk) + ["MR"]})} if level == "videos" else
+                 {f"model, IoU={thr}": get_metrics({k: [] for k in list(atk) + ["MR"]}) for thr in iou_thresholds})
+        embed_corpus(model, video_iterator, device, ops, rank, world, drained)
+        model.train(was_training)
+        return (empty, (None, None, None)) if return_topk else empty
+    shard, names, Q = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world)
+    video_index = {name: i for i, name in enumerate(names)}
+    own = np.asarray([video_index[v] for v in q_videos], np.int64)
+    pools = list(pools)
+    if len(pools) != len(own):
+        raise ValueError(f"evaluate_candidates: {len(pools)} pools for {len(own)} queries")
+    lists = engine.candidate_lists([list(p) + [int(own[q])] for q, p in enumerate(pools)], names=names)
+    K = int(return_topk)
+    if level == "videos":
+        dist, idx, vid, ranks = engine.corpus_subset_topk(shard, Q, K, lists, "videos", own_global=own, ops=ops, world=world)
+        ranks = ranks.cpu().numpy()
+        rec = {k: (ranks < k).astype(int) for k in atk}
+        rec["MR"] = ranks
+        out = {"video": get_metrics(rec)}
+    else:
+        times = [annotations[a]["times"] for a in annot_ids]
+        labels = engine.gt_labels(times, shard.counts_all[own], list(iou_thresholds), True, shard.device, ops)
+        keys = engine.best_positive_keys(shard, Q, engine.prepare_gt(shard, own, labels), ops, world)
+        if bool((keys == engine.KEY_INF).any()):
+            model.train(was_training)
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (no ground-truth-positive moment)")
+        dist, idx, vid, ranks = engine.corpus_subset_topk(shard, Q, K, lists, "moments", ops=ops, world=world, rank_keys=keys)
+        ranks = ranks.cpu().numpy()
+        out = {}
+        for r, thr in enumerate(iou_thresholds):
+            rec = {k: (ranks[r] < k).astype(int) for k in atk}
+            rec["MR"] = ranks[r]
+            out[f"model, IoU={thr}"] = get_metrics(rec)
+    model.train(was_training)
+    if return_topk:
+        return out, (dist, idx, vid)
+    return out
