@@ -261,6 +261,38 @@ int vfr_score_subset_f32(const float *Q, int64_t Nq, const float *V, const int32
                          int64_t nnz, int64_t max_list, int level, int k, float *out_dist, int64_t *out_idx, int num_rank,
                          const float *rank_dist, const int64_t *rank_idx, int64_t *count_lt, int *bad, void *workspace,
                          size_t workspace_bytes, vfr_stream_t stream);
+/* ---- sentence retrieval for moments (the reverse direction): which SENTENCES of a bank describe a probe moment best, and where
+ * a given sentence ranks among them -- the moment->sentence half of a two-way retrieval report, "describe / tag this moment" by
+ * nearest stored captions, the sentence-side hard-negative search.  S [Ns, D] = the sentence bank (the rows the other entry points
+ * take as queries); probes int32 [Nm, 3] = (video, start_t, end_t): CORPUS-GLOBAL video index and the inclusive clip span in
+ * utils.generate_moments units.  Probes need not be sorted, may repeat and may share videos; outputs are in the caller's order.
+ *   score(m, j) = (dist[s] + .. + dist[e]) / (e - s + 1), dist[c] = ||(V[c] - S[j]) + eps||_2: the canonical chain, BIT-IDENTICAL
+ *           to what vfr_score_moments_f32 writes at [j, moment id of m].  key = (fp32 bits of the score << 32) | (sent_base + j),
+ *           order (distance, sentence id) ascending.
+ *   k > 0 : out_dist / out_idx [Nm,k] = the k smallest keys over the bank's sentences as (distance, sent_base + j), padded with
+ *           (+inf, -1) when Ns < k.  k = 0 with counts only is allowed.
+ *   num_rank > 0 (<= 4): rank_dist / rank_idx / count_lt are [num_rank, Nm]; count_lt[r][m] (int64) += number of sentences of this
+ *           bank whose key sorts strictly before (rank_dist[r][m], rank_idx[r][m]).  ADDED, so sentence-bank shards chain, and their
+ *           lists merge with vfr_topk_merge_f32 (sent_base = the shard's first sentence id).
+ *   vid_base = global index of the clip bank's first video.  A probe whose video lies outside [vid_base, vid_base + Nv) belongs to
+ *           another shard and is skipped (padding, nothing added): every shard of a video-sharded bank takes the same probes.
+ *   bad (nullable, device int): set to 1 for a probe with video < 0, start_t < 0, end_t < start_t (on any shard) or end_t >= the
+ *           video's clip count (on the shard that holds the video); such a probe gives padding and adds nothing; nothing is read
+ *           or written out of bounds.
+ * Consecutive probes that name the same video share their clip distances (each (clip, sentence) distance is computed once per
+ * group of 8 probes; the sum order s -> e is fixed, so the bits do not depend on it): sort the probes by video for speed.
+ * Any D (D = 100 with 16-byte aligned S and V takes the register-resident fast path).
+ * Limits: max_clips <= 64, k <= 448, sent_base + Ns < 2^32, Nm * k < 2^31.  Bad host-side arguments: VFR_EINVAL before anything is
+ * enqueued.
+ * vfr_score_sentences_workspace_bytes = 256 + 8 k Nm C, C = min(ceil(2048 / ceil(Nm / 8)), ceil(Ns / 64), 256) >= 1 = the bound on
+ * the chunks the sentence axis is cut into (enough to fill the device when Nm is small): O(Nm k), no Nm x Ns term (0 for a bad
+ * argument).                                                                                                             */
+size_t vfr_score_sentences_workspace_bytes(int64_t Nm, int64_t Ns, int k);
+int vfr_score_sentences_f32(const float *S, int64_t Ns, const float *V, const int32_t *clip_offsets, int Nv, int total_clips,
+                            int max_clips, int D, float eps, const int32_t *probes, int64_t Nm, int64_t vid_base,
+                            int64_t sent_base, int k, float *out_dist, int64_t *out_idx, int num_rank, const float *rank_dist,
+                            const int64_t *rank_idx, int64_t *count_lt, int *bad, void *workspace, size_t workspace_bytes,
+                            vfr_stream_t stream);
 /* Device self-check of the arithmetic model the pre-filter's margins and the MFMA GEMMs' bit-exactness assume: a
  * v_mfma_f32_16x16x4_f32 = four fp32 fmas, k ascending, on its accumulator (denormals kept).  A, B [16, K] device rows
  * (K % 4 == 0; make them adversarial: wide exponent range, cancellation, denormals): C = A B^T by the matrix pipe against an

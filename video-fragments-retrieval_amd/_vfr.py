@@ -62,6 +62,9 @@ SIGNATURES = {
     "vfr_score_subset_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32]),
     "vfr_score_subset_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i64, _vp, _vp, _i64, _i64,
                                     _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vfr_score_sentences_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "vfr_score_sentences_f32": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32,
+                                       _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "vfr_topk_pack_keys": (_i32, [_vp, _vp, _i64, _vp, _vp]),
@@ -592,6 +595,58 @@ def score_subset(Q: torch.Tensor, bank: VideoBank, cand_off: torch.Tensor, cand_
                                       int(vid_base), cand_off.data_ptr(), _ptr(cand_vid) if nnz else 0, nnz, int(max_list), lv, k,
                                       _ptr(od), _ptr(oi), R, _ptr(rank_dist), _ptr(rank_idx), _ptr(count_lt), _ptr(bad),
                                       workspace.data_ptr(), nbytes, _stream()), "vfr_score_subset_f32")
+    return od, oi, count_lt
+
+
+def score_sentences(S: torch.Tensor, bank: VideoBank, probes: torch.Tensor, k: int, vid_base: int = 0, sent_base: int = 0,
+                    rank_dist=None, rank_idx=None, count_lt=None, bad: torch.Tensor | None = None,
+                    workspace: torch.Tensor | None = None, eps: float = 1e-6):
+    """Sentence retrieval for moments (include/vfr.h vfr_score_sentences_f32): per probe moment the k best sentences of the bank
+    ``S`` [Ns, D].  ``probes`` [Nm, 3] int32 = (corpus-global video, start_t, end_t), any order; ``vid_base`` = global index of the
+    bank's first video (probes of other shards give padding and add nothing); ids are ``sent_base`` + row of ``S``.
+    rank_dist / rank_idx [R, Nm] (or [Nm]), R <= 4: ``count_lt`` [R, Nm] int64 += the sentences that sort before each rank key
+    (allocated zeroed when None).  ``bad`` (device int32 [1], nullable) is set to 1 for a malformed probe.
+    The probes are handed to the library sorted by video (stable device sort, no synchronisation), so probes of one video share
+    their clip distances; results come back in the caller's order.
+    Returns (dist [Nm,k] | None, idx [Nm,k] int64 | None, count_lt | None)."""
+    S = _dev(S, torch.float32, "S")
+    probes = _dev(probes, torch.int32, "probes")
+    if probes.dim() != 2 or probes.shape[1] != 3:
+        raise RuntimeError(f"score_sentences: probes must be [Nm, 3] (video, start_t, end_t), got {tuple(probes.shape)}")
+    if S.dim() != 2 or S.shape[1] != bank.dim:
+        raise RuntimeError(f"score_sentences: S must be [Ns, {bank.dim}], got {tuple(S.shape)}")
+    Ns, Nm = int(S.shape[0]), int(probes.shape[0])
+    R = 0
+    if rank_dist is not None:
+        rank_dist = _dev(rank_dist, torch.float32, "rank_dist").reshape(-1, Nm)
+        rank_idx = _dev(rank_idx, torch.int64, "rank_idx").reshape(-1, Nm)
+        R = rank_dist.shape[0]
+        if count_lt is None:
+            count_lt = torch.zeros((R, Nm), dtype=torch.int64, device=S.device)
+        count_lt = _dev(count_lt, torch.int64, "count_lt")
+    if bad is not None:
+        bad = _dev(bad, torch.int32, "bad")
+    order = torch.sort(probes[:, 0], stable=True).indices if Nm > 1 else None
+    sp = probes if order is None else probes[order].contiguous()
+    od = torch.empty((Nm, k), dtype=torch.float32, device=S.device) if k > 0 else None
+    oi = torch.empty((Nm, k), dtype=torch.int64, device=S.device) if k > 0 else None
+    rd = ri = cl = None
+    if R:
+        rd = rank_dist if order is None else rank_dist[:, order].contiguous()
+        ri = rank_idx if order is None else rank_idx[:, order].contiguous()
+        cl = count_lt if order is None else torch.zeros_like(count_lt)
+    nbytes = lib().vfr_score_sentences_workspace_bytes(Nm, Ns, k)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=S.device)
+    _check(lib().vfr_score_sentences_f32(_ptr(S) if Ns else 0, Ns, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.num_videos,
+                                         bank.total_clips, bank.max_clips, bank.dim, eps, _ptr(sp) if Nm else 0, Nm, int(vid_base),
+                                         int(sent_base), k, _ptr(od), _ptr(oi), R, _ptr(rd), _ptr(ri), _ptr(cl), _ptr(bad),
+                                         workspace.data_ptr(), nbytes, _stream()), "vfr_score_sentences_f32")
+    if order is not None:                         # back to the caller's order
+        if k > 0:
+            od, oi = torch.empty_like(od).index_copy_(0, order, od), torch.empty_like(oi).index_copy_(0, order, oi)
+        if R:
+            count_lt.index_add_(1, order, cl)
     return od, oi, count_lt
 
 

@@ -63,6 +63,11 @@ class HipOps:
         return self.v.score_subset(Q, bank, cand_off, cand_vid, k, level, vid_base, rank_dist, rank_idx, count_lt=count_lt,
                                    workspace=workspace, bad=bad, max_list=max_list)
 
+    def score_sentences(self, S, bank, probes, k, vid_base=0, sent_base=0, rank_dist=None, rank_idx=None, count_lt=None, bad=None,
+                        workspace=None):
+        return self.v.score_sentences(S, bank, probes, k, vid_base, sent_base, rank_dist, rank_idx, count_lt=count_lt, bad=bad,
+                                      workspace=workspace)
+
     def slice_bank(self, bank, counts, v0, v1):
         return self.v.slice_bank(bank, counts, v0, v1)
 
@@ -794,6 +799,49 @@ def corpus_subset_topk(shard: CorpusShard, Q, k, lists: CandidateLists, level="m
     return od, oi, vid, cnt
 
 
+def corpus_sentence_topk(shard: CorpusShard, S, probes, k, own_sentence=None, ops=None, world=1, workspace=None):
+    """Sentence retrieval for moments over the corpus: per probe ``(global video, start_t, end_t)`` (inclusive clip span,
+    ``utils.generate_moments`` units; host array-like [Nm, 3]) the k sentences of the bank ``S`` [Ns, D] with the smallest mean clip
+    distance, in (distance, sentence index) order.  With ``own_sentence`` [Nm] (row of ``S`` that belongs to each probe) also the
+    0-based rank of that sentence = the number of sentences whose key sorts strictly before its own key for that probe (the key
+    comes from one own-video scoring launch on the rank that holds the video).  ``world`` > 1: the clip bank is sharded by video,
+    ``S`` is replicated and every rank passes the same probes; the ranks that do not hold a probe's video emit padding and zero,
+    so the lists merge with the key merge and the counts add.  A probe with a span outside its video gives padding and rank 0.
+    Returns (dist [Nm,k], sentence index [Nm,k] int64 (-1 = padding), ranks [Nm] int64 | None); dist / index are None for k = 0."""
+    ops = ops or HipOps()
+    pr = np.asarray(probes.cpu() if isinstance(probes, torch.Tensor) else probes, np.int64).reshape(-1, 3)
+    Nm, Ns = len(pr), int(S.shape[0])
+    rd = ri = None
+    if own_sentence is not None:
+        own = np.asarray(own_sentence.cpu() if isinstance(own_sentence, torch.Tensor) else own_sentence, np.int64).reshape(-1)
+        if len(own) != Nm:
+            raise ValueError(f"corpus_sentence_topk: {len(own)} own sentences for {Nm} probes")
+        if Nm and (own.min() < 0 or own.max() >= Ns):
+            raise ValueError(f"corpus_sentence_topk: own_sentence out of range [0, {Ns})")
+        gv, s0, e0 = pr[:, 0], pr[:, 1], pr[:, 2]
+        mine = (gv >= shard.lo) & (gv < shard.hi) & (s0 >= 0) & (e0 >= s0)
+        n = np.where(mine, shard.counts_all[np.clip(gv, 0, max(shard.num_videos_all - 1, 0))], 0) if shard.num_videos_all else np.zeros(Nm, np.int64)
+        mine &= e0 < n
+        rd = torch.full((Nm,), float("inf"), dtype=torch.float32, device=shard.device)
+        ri = torch.from_numpy(own).to(shard.device)
+        sel = np.nonzero(mine)[0]
+        if len(sel):
+            sel_t = torch.from_numpy(sel).to(shard.device)
+            sc = ops.score_own(S[ri[sel_t]].contiguous(), shard.bank, torch.from_numpy((gv[sel] - shard.lo).astype(np.int32)).to(shard.device))
+            ns, ss, es = n[sel], s0[sel], e0[sel]
+            col = np.where(ss == es, ss, ns + (ss * (2 * ns - ss - 1)) // 2 + (es - ss - 1))     # utils.generate_moments position
+            rd[sel_t] = sc[torch.arange(len(sel), device=sc.device), torch.from_numpy(col).to(sc.device)]
+    probes_t = torch.from_numpy(pr.astype(np.int32)).to(shard.device)
+    od, oi, cnt = ops.score_sentences(S, shard.bank, probes_t, k, shard.lo, 0, rd, ri, workspace=workspace)
+    dist = _group(world)
+    if dist is not None:
+        if k > 0:
+            od, oi = gather_merge_topk(od, oi, ops, world)
+        if cnt is not None:
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+    return od, oi, (cnt[0] if cnt is not None else None)
+
+
 def video_results(ids, dist, names, counts_all, mom_off_all):
     """Search results as rows: per query a list of (video name, start_t, end_t, distance) for the global moment ids ``ids``
     [Nq, k] (``corpus_video_topk`` / ``corpus_topk``); start_t / end_t are the inclusive clip span of the moment
@@ -1103,6 +1151,55 @@ class TorchCpuOps:
             od, oi = _unpack_key(srt)
             od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
             oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
+        if R == 0:
+            counts = None
+        elif count_lt is not None:
+            counts = counts + count_lt
+        return od, oi, counts
+
+    def score_sentences(self, S, bank, probes, k, vid_base=0, sent_base=0, rank_dist=None, rank_idx=None, count_lt=None, bad=None,
+                        workspace=None, eps=1e-6):
+        """Sentence retrieval for moments from dense torch arithmetic (same semantics as ``_vfr.score_sentences``): per probe
+        (global video, start_t, end_t) the mean clip distance of every sentence of ``S``, keys (score, sent_base + row), the k
+        smallest, and the keys below each rank key.  Probes of other shards or with a bad span give padding and add nothing."""
+        S = S.float()
+        Ns = S.shape[0]
+        rows = [[int(x) for x in r] for r in torch.as_tensor(probes).tolist()]
+        Nm = len(rows)
+        off = bank.clip_off.tolist()
+        Nv = len(off) - 1
+        kstar = None
+        if rank_dist is not None:
+            kstar = _pack_key(rank_dist.reshape(-1, Nm).contiguous(), rank_idx.reshape(-1, Nm))
+        R = 0 if kstar is None else kstar.shape[0]
+        counts = torch.zeros((R, Nm), dtype=torch.int64)
+        ids = sent_base + torch.arange(Ns)
+        out = torch.full((Nm, k), KEY_INF, dtype=torch.int64)
+        for m, (gv, s0, e0) in enumerate(rows):
+            wrong = gv < 0 or s0 < 0 or e0 < s0
+            lv = gv - vid_base
+            owned = gv >= 0 and 0 <= lv < Nv
+            if owned and e0 >= off[lv + 1] - off[lv]:
+                wrong = True
+            if wrong and bad is not None:
+                bad.fill_(1)
+            if wrong or not owned:
+                continue
+            V = bank.emb[off[lv] + s0:off[lv] + e0 + 1]
+            d = ((V[None, :, :] - S[:, None, :]) + eps).pow(2).sum(-1).sqrt()
+            acc = d[:, 0]
+            for c in range(1, d.shape[1]):
+                acc = acc + d[:, c]
+            keys = _pack_key(acc / float(e0 - s0 + 1), ids)
+            if R:
+                counts[:, m] = (keys[None, :] < kstar[:, m, None]).sum(dim=1)
+            srt = keys.sort().values[:k]
+            out[m, :srt.numel()] = srt
+        od = oi = None
+        if k > 0:
+            od, oi = _unpack_key(out)
+            od = torch.where(out == KEY_INF, torch.full_like(od, float("inf")), od)
+            oi = torch.where(out == KEY_INF, torch.full_like(oi, -1), oi)
         if R == 0:
             counts = None
         elif count_lt is not None:

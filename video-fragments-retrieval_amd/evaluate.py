@@ -323,3 +323,61 @@ def evaluate_candidates(model, video_iterator, lang_iterator, annotations, devic
     if return_topk:
         return out, (dist, idx, vid)
     return out
+
+
+def sentence_probes(annotations, annot_ids, own, counts_all):
+    """The probe moment of each annotation: the evaluation-mode positive of the reference's ``CustomBatchSampler``
+    (``model/data.py:289-291``) -- the most common annotated span (``Counter(...).most_common()[0][0]``: the first seen wins a
+    tie) -- among the spans that lie inside the video (``0 <= s <= e <= n - 1``).  ``own`` [Nq] = global video index per
+    annotation.  Returns (probes [P, 3] int64 = (video, start_t, end_t), rows [P] = positions in ``annot_ids`` that got a probe)."""
+    from collections import Counter
+    probes, rows = [], []
+    for q, a in enumerate(annot_ids):
+        n = int(counts_all[own[q]])
+        spans = [(int(t[0]), int(t[1])) for t in annotations[a]["times"]]
+        spans = [(s, e) for s, e in spans if 0 <= s <= e <= n - 1]
+        if not spans:
+            continue
+        s, e = Counter(spans).most_common()[0][0]
+        probes.append((int(own[q]), s, e))
+        rows.append(q)
+    return np.asarray(probes, np.int64).reshape(-1, 3), np.asarray(rows, np.int64)
+
+
+def evaluate_sentences(model, video_iterator, lang_iterator, annotations, device, atk=(1, 10, 100), rank=0, world=1,
+                       return_topk=0):
+    """Sentence retrieval (moment -> sentence) metrics of the same iterators ``evaluate`` consumes: given an annotation's moment,
+    where does its own sentence rank among ALL sentences of ``lang_iterator``.
+
+    The probe of an annotation is ``sentence_probes``' span (the reference sampler's evaluation-mode positive); the sentence bank
+    is every query of ``lang_iterator`` -- other sentences of the same video, and other annotations of the same moment, compete
+    like any other sentence.  The 0-based rank is the number of sentences whose (score, sentence index) key sorts before the own
+    sentence's key (``engine.corpus_sentence_topk``).  Returns ``{"sentence": {"R@1", "R@10", "R@100", "MR"}}`` (``get_metrics``,
+    as ``evaluate_videos``); annotations without a span inside their video get no probe and are counted in
+    ``out["sentence"]["skipped"]`` (present only when non-zero).  With ``return_topk`` = k also ``(dist, sentence idx, annotation
+    rows)``: [P, k] lists of the probes and the positions in the iteration order they belong to."""
+    was_training = model.training
+    model.eval()
+    ops = engine.ops_for(device)
+    drained = _drain_videos(video_iterator)
+    tokens, q_videos, annot_ids = _drain_queries(lang_iterator)
+    if not tokens:
+        embed_corpus(model, video_iterator, device, ops, rank, world, drained)
+        model.train(was_training)
+        out = {"sentence": get_metrics({k: [] for k in list(atk) + ["MR"]})}
+        return (out, (None, None, None)) if return_topk else out
+    shard, names, S = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world)
+    video_index = {name: i for i, name in enumerate(names)}
+    own = np.asarray([video_index[v] for v in q_videos], np.int64)
+    probes, rows = sentence_probes(annotations, annot_ids, own, shard.counts_all)
+    dist, idx, ranks = engine.corpus_sentence_topk(shard, S, probes, int(return_topk), rows, ops, world)
+    ranks = ranks.cpu().numpy()
+    model.train(was_training)
+    rec = {k: (ranks < k).astype(int) for k in atk}
+    rec["MR"] = ranks
+    out = {"sentence": get_metrics(rec)}
+    if len(rows) < len(annot_ids):
+        out["sentence"]["skipped"] = len(annot_ids) - len(rows)
+    if return_topk:
+        return out, (dist, idx, rows)
+    return out
