@@ -782,6 +782,72 @@ def test_prefilter_bank_products_reused_only_while_valid(vfr, mode):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("wrapper", ["topk-exact", "topk-mfma", "video", "subset-moments", "subset-videos", "sentences", "nms"])
+def test_scoring_wrapper_contracts(vfr, wrapper, monkeypatch):
+    """What the scoring wrappers share (output lists, rank keys and counts, workspace reuse), as equalities between calls on one
+    small ragged bank: [N] keys == [1, N] keys; a caller's ``count_lt`` is ADDED to, in place; k == 0 returns no lists; a too
+    small workspace is replaced, a large enough one is used as passed and gives the same bits again."""
+    rs = np.random.RandomState(11)
+    off = synth.clip_offsets(np.asarray([1, 2, 3, 6, 4]))
+    bank = vfr.VideoBank(dev(rs.randn(int(off[-1]), 100).astype(np.float32) * 0.3 + 0.5), dev(off.astype(np.int32)))
+    Q = dev(rs.randn(3, 100).astype(np.float32) * 0.3 + 0.5)
+    S = dev(rs.randn(7, 100).astype(np.float32) * 0.3 + 0.5)
+    probes = dev(np.asarray([[3, 1, 4], [1, 0, 1], [3, 0, 0]], np.int32))                 # two probes on video 3, not sorted
+    cand_off, cand_vid = dev(np.asarray([0, 3, 4, 7], np.int64)), dev(np.asarray([0, 1, 3, 3, 1, 2, 4], np.int32))
+    used = []
+    pick = vfr._workspace
+    monkeypatch.setattr(vfr, "_workspace", lambda ws, nbytes, device: used.append(pick(ws, nbytes, device)) or used[-1])
+
+    def call(k, rd=None, ri=None, cnt=None, ws=None):
+        if wrapper.startswith("topk"):
+            return vfr.score_topk(Q, bank, k, rd, ri, count_lt=cnt, workspace=ws, mode=wrapper[5:])
+        if wrapper == "video":
+            return vfr.score_video_topk(Q, bank, k, rd, ri, count=cnt, workspace=ws)
+        if wrapper == "nms":
+            return vfr.score_moment_nms(Q, bank, k, per_video=2, nms_iou=0.5, workspace=ws) + (None,)
+        if wrapper == "sentences":
+            return vfr.score_sentences(S, bank, probes, k, rank_dist=rd, rank_idx=ri, count_lt=cnt, workspace=ws)
+        return vfr.score_subset(Q, bank, cand_off, cand_vid, k, wrapper[7:], rank_dist=rd, rank_idx=ri, count_lt=cnt, workspace=ws)
+
+    vfr.set_option("score_mfma_min", 0)                  # the five-video bank reaches the MFMA paths (and their workspace claims)
+    try:
+        # rank keys = existing entries of each row's full sorted list: position p has exactly p keys before it (strictly)
+        full_d, full_i, _ = call(41)
+        pos = {"video": [[2, 0, 4]], "subset-videos": [[0, 0, 0], [2, 0, 1]], "nms": []}.get(wrapper, [[0, 3, 1], [5, 2, 6]])
+        for R in range(1, len(pos) + 1):
+            at = torch.tensor(pos[:R], device=DEV).t()                                   # [N, R]
+            assert bool((full_i.gather(1, at) >= 0).all())
+            rd, ri = full_d.gather(1, at).t().contiguous(), full_i.gather(1, at).t().contiguous()
+            flat = wrapper == "video"                                                     # its keys and counts are [N]
+            if flat:
+                rd, ri = rd[0], ri[0]
+            for k in (0, 2):
+                d, i, c = call(k, rd, ri)
+                assert c.shape == rd.shape and c.dtype == torch.int64 and torch.equal(c, torch.tensor(pos[:R], device=DEV).reshape(c.shape))
+                assert (d is None and i is None) if k == 0 else (torch.equal(d, full_d[:, :2]) and torch.equal(i, full_i[:, :2]))
+                if R == 1:                                                                # [N] keys == [1, N] keys
+                    c1 = call(k, rd.reshape(-1), ri.reshape(-1))[2]
+                    c2 = call(k, rd.reshape(1, -1), ri.reshape(1, -1))[2]
+                    assert torch.equal(c1.reshape(-1), c.reshape(-1)) and torch.equal(c2.reshape(-1), c.reshape(-1))
+                mine = torch.arange(c.numel(), device=DEV).reshape(c.shape) + 7
+                before = mine.clone()
+                assert call(k, rd, ri, cnt=mine)[2] is mine and torch.equal(mine, before + c)
+        if wrapper == "nms":
+            d0, i0, _ = call(0)
+            assert tuple(d0.shape) == (3, 0) and tuple(i0.shape) == (3, 0) and d0.dtype == torch.float32 and i0.dtype == torch.int64
+        d, i, _ = call(2)
+        tiny = torch.empty(1, dtype=torch.uint8, device=DEV)
+        dt, it, _ = call(2, ws=tiny)
+        assert torch.equal(dt, d) and torch.equal(it, i)
+        big = torch.empty(1 << 26, dtype=torch.uint8, device=DEV)                         # (score_topk asks for ~18 MB at any size)
+        for _ in range(2):                                                                # the second call may reuse what the first left
+            db, ib, _ = call(2, ws=big)
+            assert used[-1] is big and torch.equal(db, d) and torch.equal(ib, i)
+    finally:
+        vfr.set_option("score_mfma_min", 128)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("normlang", [False, True])
 def test_bilstm_few_queries_vector_chain(vfr, oracle, normlang):
     """Batches of 1-4 queries (a serving request) take the vector-chain LSTM step (`lstm_small`; one or two queries: the

@@ -472,3 +472,56 @@ def test_resnet_plan_and_frame_selection_host_side(oracle):
     idx = features.sample_frames(900, 30.0, 6)
     assert sel.dtype == torch.uint8 and sel.shape == (150, 2, 2, 3) and np.array_equal(sel.numpy(), fr[idx])
     assert features.select_frames(fr[:7], 0.0, 6).shape == (7, 2, 2, 3)
+
+
+def _tiny_eval_problem(no_positive):
+    """4 videos of 1..4 clips, 3 queries; ``no_positive``: query 0 keeps ONE annotator, so no moment of its video is positive."""
+    counts = np.arange(1, 5, dtype=np.int32)
+    seg, ctx = synth.video_features(counts, 64, seed=5)
+    tokens = synth.query_tokens(3, vocab=400, seed=5)
+    own, times = synth.annotations(3, counts, seed=5)
+    if no_positive:
+        times[0] = [[0, 0]]
+    model = make_model(synth.model_weights(64, vocab=400, hidden=16, seed=5), feat_dim=64, hidden=16)
+    return MemoryDataset(seg, ctx, counts, tokens, own, times), model
+
+
+EVAL_ENTRY_POINTS = {
+    "evaluate": (lambda m, vi, li, ann: vevaluate.evaluate(m, vi, li, ann, "cpu"), True),
+    "evaluate_videos": (lambda m, vi, li, ann: vevaluate.evaluate_videos(m, vi, li, ann, "cpu"), False),
+    "evaluate_moments_nms": (lambda m, vi, li, ann: vevaluate.evaluate_moments_nms(m, vi, li, ann, "cpu", per_video=2), False),
+    "evaluate_candidates": (lambda m, vi, li, ann: vevaluate.evaluate_candidates(m, vi, li, ann, "cpu", [[0], [1, 2], []]), True),
+    "evaluate_sentences": (lambda m, vi, li, ann: vevaluate.evaluate_sentences(m, vi, li, ann, "cpu"), False),
+}
+
+
+@pytest.mark.parametrize("name", sorted(EVAL_ENTRY_POINTS))
+def test_entry_points_restore_the_models_mode(name):
+    """Every evaluator leaves ``model.training`` as it found it: after a normal return, and after the IndexError of a query
+    without a ground-truth-positive moment (the entry points that rank positives still raise it)."""
+    run, raises = EVAL_ENTRY_POINTS[name]
+    ds, model = _tiny_eval_problem(no_positive=True)
+    model.train()
+    if raises:
+        with pytest.raises(IndexError, match="no ground-truth-positive moment"):
+            run(model, *ds.iterators(), ds.annotations)
+    else:
+        assert run(model, *ds.iterators(), ds.annotations)
+    assert model.training is True
+    ds, model = _tiny_eval_problem(no_positive=False)
+    model.train()
+    assert run(model, *ds.iterators(), ds.annotations) and model.training is True
+    model.eval()
+    assert run(model, *ds.iterators(), ds.annotations) and model.training is False
+
+
+def test_rank_and_empty_metrics_equal_the_literals_they_replace():
+    atk = (1, 10, 100)
+    for ranks in (np.asarray([0, 3, 9, 10, 150], np.int64), np.zeros(0, np.int64)):
+        got = vevaluate._rank_metrics(ranks, atk)
+        want = {1: (ranks < 1).astype(int), 10: (ranks < 10).astype(int), 100: (ranks < 100).astype(int), "MR": ranks}
+        assert list(got) == list(want) and all(np.array_equal(got[k], want[k]) and got[k].dtype == want[k].dtype for k in want)
+    got = vevaluate._empty_metrics(atk, True)
+    assert got == {1: [], 10: [], 100: [], "MR": []} and list(got) == [1, 10, 100, "MR"]
+    got = vevaluate._empty_metrics(atk, False)
+    assert got == {k: [] for k in atk} and list(got) == [1, 10, 100]

@@ -148,6 +148,40 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _workspace(workspace, nbytes: int, device) -> torch.Tensor:
+    """The caller's workspace when it is large enough (the SAME object: the ``_vfr_bank`` claim lives on it), else a new one."""
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=device)
+    return workspace
+
+
+def _out_lists(n: int, k: int, device):
+    """(dist fp32 [n, k], idx int64 [n, k]) to be filled by a kernel; (None, None) for k == 0."""
+    if k == 0:
+        return None, None
+    return torch.empty((n, k), dtype=torch.float32, device=device), torch.empty((n, k), dtype=torch.int64, device=device)
+
+
+def _rank_keys(rank_dist, rank_idx, count_lt, n: int, device, what=("rank_dist", "rank_idx", "count_lt")):
+    """Rank keys [R, n] (or [n]) of a scoring wrapper -> (rank_dist [R, n], rank_idx [R, n], count_lt, R): ``count_lt`` is
+    allocated zeroed [R, n] when None, else checked and ADDED to by the kernel.  No keys: R == 0, nothing is touched."""
+    if rank_dist is None:
+        return rank_dist, rank_idx, count_lt, 0
+    rank_dist = _dev(rank_dist, torch.float32, what[0]).reshape(-1, n)
+    rank_idx = _dev(rank_idx, torch.int64, what[1]).reshape(-1, n)
+    R = rank_dist.shape[0]
+    if count_lt is None:
+        count_lt = torch.zeros((R, n), dtype=torch.int64, device=device)
+    return rank_dist, rank_idx, _dev(count_lt, torch.int64, what[2]), R
+
+
+def csr_offsets(counts):
+    """Host clip counts per video -> (clip offsets, moment offsets), int64 [Nv + 1] each (a video of n clips has n (n + 1) / 2
+    moments)."""
+    counts = np.asarray(counts, np.int64)
+    return np.concatenate([[0], np.cumsum(counts)]), np.concatenate([[0], np.cumsum(counts * (counts + 1) // 2)])
+
+
 def set_option(name: str, value: int) -> None:
     _check(lib().vfr_set_option(name.encode(), int(value)), "vfr_set_option")
 
@@ -252,7 +286,7 @@ def visual_mlp(seg, ctx, clip_off, W1, b1, W2, b2) -> torch.Tensor:
         raise RuntimeError("visual_mlp: inconsistent shapes")
     out = torch.empty((C, D), dtype=torch.float32, device=seg.device)
     ws_bytes = lib().vfr_visual_mlp_workspace_bytes(C, Nv, F, hid)
-    ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=seg.device)
+    ws = _workspace(None, ws_bytes, seg.device)
     _check(lib().vfr_visual_mlp_f32(seg.data_ptr(), ctx.data_ptr(), clip_off.data_ptr(), Nv, C, F, W1.data_ptr(),
                                     b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), hid, D, out.data_ptr(), ws.data_ptr(),
                                     ws_bytes, _stream()), "vfr_visual_mlp_f32")
@@ -285,7 +319,7 @@ def bilstm_final(tokens, emb, lstm: dict, Wfc, bfc, len_tab=None) -> torch.Tenso
     poll_faults()                              # (a give-up of an EARLIER call's sequence kernel: repaired there, reported here)
     out = torch.empty((B, D), dtype=torch.float32, device=tokens.device)
     nbytes = lib().vfr_bilstm_workspace_bytes(B, T, E, H, emb.shape[0])
-    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=tokens.device)
+    ws = _workspace(None, nbytes, tokens.device)
     _check(lib().vfr_bilstm_final_f32(tokens.data_ptr(), B, T, emb.data_ptr(), emb.shape[0], _ptr(lt),
                                       *[w.data_ptr() for w in ws_], E, H, Wfc.data_ptr(), bfc.data_ptr(), D,
                                       out.data_ptr(), ws.data_ptr(), nbytes, _stream()), "vfr_bilstm_final_f32")
@@ -339,11 +373,8 @@ class VideoBank:
 
 def slice_bank(bank: VideoBank, counts, v0: int, v1: int) -> VideoBank:
     """Videos [v0, v1) of ``bank`` as a bank of their own (``counts`` = host clip counts of ``bank``'s videos)."""
-    import numpy as np
-    counts = np.asarray(counts, np.int64)
-    off = np.concatenate([[0], np.cumsum(counts)])
-    mom = np.concatenate([[0], np.cumsum(counts * (counts + 1) // 2)])
-    sub = counts[v0:v1]
+    off, mom = csr_offsets(counts)
+    sub = np.asarray(counts, np.int64)[v0:v1]
     clip_off = bank.clip_off[v0:v1 + 1] if v0 == 0 else bank.clip_off[v0:v1 + 1] - bank.clip_off[v0]   # on the device
     mom_off = bank.mom_off[v0:v1 + 1] if v0 == 0 else bank.mom_off[v0:v1 + 1] - bank.mom_off[v0]
     return VideoBank(bank.emb[int(off[v0]):int(off[v1])], clip_off.contiguous(), bank.id_base + int(mom[v0]),
@@ -418,6 +449,12 @@ def _mfma_mode_ok(device) -> bool:
     return ok
 
 
+def _bank_args(Q: torch.Tensor, bank: VideoBank, eps: float):
+    """The leading arguments the bank-scoring entry points share (include/vfr.h): queries, the bank's CSR, eps, id base."""
+    return (Q.data_ptr(), Q.shape[0], bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.mom_off.data_ptr(), bank.num_videos,
+            bank.total_clips, bank.min_clips, bank.max_clips, bank.dim, eps, bank.id_base)
+
+
 def score_topk(Q: torch.Tensor, bank: VideoBank, k: int, rank_dist=None, rank_idx=None, count_lt=None,
                eps: float = 1e-6, workspace: torch.Tensor | None = None, thr_seed: torch.Tensor | None = None,
                mode: str | None = None):
@@ -433,16 +470,8 @@ def score_topk(Q: torch.Tensor, bank: VideoBank, k: int, rank_dist=None, rank_id
     if mode != "exact" and not _mfma_mode_ok(Q.device):
         mode = "exact"
     Nq = Q.shape[0]
-    od = torch.empty((Nq, k), dtype=torch.float32, device=Q.device) if k > 0 else None
-    oi = torch.empty((Nq, k), dtype=torch.int64, device=Q.device) if k > 0 else None
-    R = 0
-    if rank_dist is not None:
-        rank_dist = _dev(rank_dist, torch.float32, "rank_dist").reshape(-1, Nq)
-        rank_idx = _dev(rank_idx, torch.int64, "rank_idx").reshape(-1, Nq)
-        R = rank_dist.shape[0]
-        if count_lt is None:
-            count_lt = torch.zeros((R, Nq), dtype=torch.int64, device=Q.device)
-        count_lt = _dev(count_lt, torch.int64, "count_lt")
+    od, oi = _out_lists(Nq, k, Q.device)
+    rank_dist, rank_idx, count_lt, R = _rank_keys(rank_dist, rank_idx, count_lt, Nq, Q.device)
     if thr_seed is not None:
         thr_seed = _dev(thr_seed, torch.int64, "thr_seed")
     dtype = SCORE_MODES[mode]
@@ -450,11 +479,8 @@ def score_topk(Q: torch.Tensor, bank: VideoBank, k: int, rank_dist=None, rank_id
         nbytes = lib().vfr_score_topk_workspace_bytes(Nq, bank.num_videos, k)
     else:
         nbytes = lib().vfr_score_topk_mfma_workspace_bytes(Nq, bank.num_videos, bank.total_clips, k)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=Q.device)
-    common = (Q.data_ptr(), Nq, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.mom_off.data_ptr(), bank.num_videos,
-              bank.total_clips, bank.min_clips, bank.max_clips, bank.dim, eps, bank.id_base, k, _ptr(od), _ptr(oi), R,
-              _ptr(rank_dist), _ptr(rank_idx), _ptr(count_lt), _ptr(thr_seed))
+    workspace = _workspace(workspace, nbytes, Q.device)
+    common = _bank_args(Q, bank, eps) + (k, _ptr(od), _ptr(oi), R, _ptr(rank_dist), _ptr(rank_idx), _ptr(count_lt), _ptr(thr_seed))
     if dtype is None:
         workspace._vfr_bank = None               # the exact kernels carve the workspace their own way
         _check(lib().vfr_score_topk_f32(*common, workspace.data_ptr(), nbytes, _stream()), "vfr_score_topk_f32")
@@ -475,6 +501,33 @@ def score_topk(Q: torch.Tensor, bank: VideoBank, k: int, rank_dist=None, rank_id
 VIDEO_EXACT = 2                            # include/vfr.h VFR_SCORE_EXACT
 
 
+def _video_mode(mode, Q, who: str):
+    """``mode`` of the video-level wrappers ("mfma" | "exact", None = DEFAULT_SCORE_MODE; a device that fails the MFMA
+    self-check gets "exact") -> (the library's dtype word, the checked ``Q``)."""
+    mode = mode or DEFAULT_SCORE_MODE
+    if mode not in ("exact", "mfma"):
+        raise RuntimeError(f"{who}: unsupported mode {mode!r} (exact, mfma)")
+    Q = _dev(Q, torch.float32, "Q")
+    if mode == "mfma" and not _mfma_mode_ok(Q.device):
+        mode = "exact"
+    return (VIDEO_EXACT if mode == "exact" else SCORE_MODES["mfma"]), Q
+
+
+def _video_bank_ready(workspace: torch.Tensor, bank: VideoBank, dtype: int, eps: float):
+    """Before a video-level call: (token, may the call CLAIM the bank-side products a previous call left in ``workspace``);
+    the workspace's claim is dropped until ``_video_bank_claim`` renews it."""
+    token = ("video",) + bank.prep_token(0, eps)
+    ready = dtype == 0 and getattr(workspace, "_vfr_bank", None) == token
+    workspace._vfr_bank = None
+    return token, ready
+
+
+def _video_bank_claim(workspace: torch.Tensor, token, bank: VideoBank, dtype: int, ran: bool = True) -> None:
+    """After the call: when the MFMA fast path ran (``ran``: the call had work at all), its bank-side products are in the workspace."""
+    if ran and dtype == 0 and bank.dim == 100 and bank.max_clips <= 21 and bank.num_videos >= max(1, get_option("score_mfma_min")):
+        workspace._vfr_bank = token
+
+
 def score_video_topk(Q: torch.Tensor, bank: VideoBank, k: int, own_dist=None, own_idx=None, count=None,
                      mode: str | None = None, workspace: torch.Tensor | None = None, eps: float = 1e-6):
     """Video-level retrieval (include/vfr.h vfr_score_video_topk_f32): the k best DISTINCT videos per query, each as
@@ -483,36 +536,22 @@ def score_video_topk(Q: torch.Tensor, bank: VideoBank, k: int, own_dist=None, ow
     bank's videos whose best key sorts before it (allocated zeroed when None).  ``mode``: "mfma" (MFMA bounds + exact
     triangles where they cannot decide) or "exact"; None = DEFAULT_SCORE_MODE.  Both give the same bits.
     Returns (dist [Nq,k] | None, idx [Nq,k] int64 | None, count | None)."""
-    mode = mode or DEFAULT_SCORE_MODE
-    if mode not in ("exact", "mfma"):
-        raise RuntimeError(f"score_video_topk: unsupported mode {mode!r} (exact, mfma)")
-    Q = _dev(Q, torch.float32, "Q")
-    if mode == "mfma" and not _mfma_mode_ok(Q.device):
-        mode = "exact"
+    dtype, Q = _video_mode(mode, Q, "score_video_topk")
     Nq = Q.shape[0]
-    od = torch.empty((Nq, k), dtype=torch.float32, device=Q.device) if k > 0 else None
-    oi = torch.empty((Nq, k), dtype=torch.int64, device=Q.device) if k > 0 else None
-    if own_dist is not None:
-        own_dist = _dev(own_dist, torch.float32, "own_dist").reshape(Nq)
-        own_idx = _dev(own_idx, torch.int64, "own_idx").reshape(Nq)
+    od, oi = _out_lists(Nq, k, Q.device)
+    own_dist, own_idx, cnt, R = _rank_keys(own_dist, own_idx, count, Nq, Q.device, ("own_dist", "own_idx", "count"))
+    if R:                                    # ONE key per query, and the public count is [Nq]
+        own_dist, own_idx = own_dist.reshape(Nq), own_idx.reshape(Nq)
         if count is None:
-            count = torch.zeros((Nq,), dtype=torch.int64, device=Q.device)
-        count = _dev(count, torch.int64, "count")
-    dtype = VIDEO_EXACT if mode == "exact" else SCORE_MODES["mfma"]
+            cnt = cnt.reshape(Nq)
     nbytes = lib().vfr_score_video_topk_workspace_bytes(Nq, bank.num_videos, bank.total_clips, k)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=Q.device)
-    token = ("video",) + bank.prep_token(0, eps)
-    ready = dtype == 0 and getattr(workspace, "_vfr_bank", None) == token
-    workspace._vfr_bank = None
-    _check(lib().vfr_score_video_topk_f32(Q.data_ptr(), Nq, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.mom_off.data_ptr(),
-                                          bank.num_videos, bank.total_clips, bank.min_clips, bank.max_clips, bank.dim, eps,
-                                          bank.id_base, k, _ptr(od), _ptr(oi), _ptr(own_dist), _ptr(own_idx), _ptr(count),
+    workspace = _workspace(workspace, nbytes, Q.device)
+    token, ready = _video_bank_ready(workspace, bank, dtype, eps)
+    _check(lib().vfr_score_video_topk_f32(*_bank_args(Q, bank, eps), k, _ptr(od), _ptr(oi), _ptr(own_dist), _ptr(own_idx), _ptr(cnt),
                                           dtype | (MFMA_BANK_READY if ready else 0), workspace.data_ptr(), nbytes, _stream()),
            "vfr_score_video_topk_f32")
-    if dtype == 0 and bank.dim == 100 and bank.max_clips <= 21 and bank.num_videos >= max(1, get_option("score_mfma_min")):
-        workspace._vfr_bank = token          # the fast path ran: the bank-side products are in the workspace
-    return od, oi, count
+    _video_bank_claim(workspace, token, bank, dtype)
+    return od, oi, cnt
 
 
 def score_moment_nms(Q: torch.Tensor, bank: VideoBank, k: int, per_video: int = 0, nms_iou: float = 1.0,
@@ -522,30 +561,18 @@ def score_moment_nms(Q: torch.Tensor, bank: VideoBank, k: int, per_video: int = 
     moment of its video is > ``nms_iou`` is suppressed, and at most ``per_video`` are accepted (0 = no cap).  Padded with
     (+inf, -1).  ``per_video`` = 1 is ``score_video_topk``; no cap and ``nms_iou`` >= 1 is ``score_topk``.  ``mode``:
     "mfma" or "exact" (same bits); None = DEFAULT_SCORE_MODE.  Returns (dist [Nq,k], idx [Nq,k] int64)."""
-    mode = mode or DEFAULT_SCORE_MODE
-    if mode not in ("exact", "mfma"):
-        raise RuntimeError(f"score_moment_nms: unsupported mode {mode!r} (exact, mfma)")
-    Q = _dev(Q, torch.float32, "Q")
-    if mode == "mfma" and not _mfma_mode_ok(Q.device):
-        mode = "exact"
+    dtype, Q = _video_mode(mode, Q, "score_moment_nms")
     Nq = Q.shape[0]
-    od = torch.empty((Nq, k), dtype=torch.float32, device=Q.device)
-    oi = torch.empty((Nq, k), dtype=torch.int64, device=Q.device)
-    dtype = VIDEO_EXACT if mode == "exact" else SCORE_MODES["mfma"]
+    od, oi = _out_lists(Nq, k, Q.device)
+    if k == 0:                               # this wrapper returns lists only, and never None
+        od, oi = Q.new_empty((Nq, 0)), Q.new_empty((Nq, 0), dtype=torch.int64)
     nbytes = lib().vfr_score_moment_nms_workspace_bytes(Nq, bank.num_videos, bank.total_clips, k, int(per_video))
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=Q.device)
-    token = ("video",) + bank.prep_token(0, eps)        # the workspace front is score_video_topk's
-    ready = dtype == 0 and getattr(workspace, "_vfr_bank", None) == token
-    workspace._vfr_bank = None
-    _check(lib().vfr_score_moment_nms_f32(Q.data_ptr(), Nq, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.mom_off.data_ptr(),
-                                          bank.num_videos, bank.total_clips, bank.min_clips, bank.max_clips, bank.dim, eps,
-                                          bank.id_base, k, int(per_video), float(nms_iou), _ptr(od), _ptr(oi),
+    workspace = _workspace(workspace, nbytes, Q.device)
+    token, ready = _video_bank_ready(workspace, bank, dtype, eps)       # the workspace front is score_video_topk's
+    _check(lib().vfr_score_moment_nms_f32(*_bank_args(Q, bank, eps), k, int(per_video), float(nms_iou), _ptr(od), _ptr(oi),
                                           dtype | (MFMA_BANK_READY if ready else 0), workspace.data_ptr(), nbytes, _stream()),
            "vfr_score_moment_nms_f32")
-    if k > 0 and Nq > 0 and dtype == 0 and bank.dim == 100 and bank.max_clips <= 21 and \
-            bank.num_videos >= max(1, get_option("score_mfma_min")):
-        workspace._vfr_bank = token          # the fast path ran: the bank-side products are in the workspace
+    _video_bank_claim(workspace, token, bank, dtype, ran=k > 0 and Nq > 0)
     return od, oi
 
 
@@ -574,25 +601,15 @@ def score_subset(Q: torch.Tensor, bank: VideoBank, cand_off: torch.Tensor, cand_
     nnz = int(cand_vid.numel())
     if max_list is None:
         max_list = int((cand_off[1:] - cand_off[:-1]).max()) if Nq > 0 else 0
-    od = torch.empty((Nq, k), dtype=torch.float32, device=Q.device) if k > 0 else None
-    oi = torch.empty((Nq, k), dtype=torch.int64, device=Q.device) if k > 0 else None
-    R = 0
-    if rank_dist is not None:
-        rank_dist = _dev(rank_dist, torch.float32, "rank_dist").reshape(-1, Nq)
-        rank_idx = _dev(rank_idx, torch.int64, "rank_idx").reshape(-1, Nq)
-        R = rank_dist.shape[0]
-        if count_lt is None:
-            count_lt = torch.zeros((R, Nq), dtype=torch.int64, device=Q.device)
-        count_lt = _dev(count_lt, torch.int64, "count_lt")
+    od, oi = _out_lists(Nq, k, Q.device)
+    rank_dist, rank_idx, count_lt, R = _rank_keys(rank_dist, rank_idx, count_lt, Nq, Q.device)
     if bad is not None:
         bad = _dev(bad, torch.int32, "bad")
     lv = SUBSET_LEVELS[level]
     nbytes = lib().vfr_score_subset_workspace_bytes(Nq, nnz, int(max_list), k, lv)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=Q.device)
-    _check(lib().vfr_score_subset_f32(Q.data_ptr(), Nq, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.mom_off.data_ptr(),
-                                      bank.num_videos, bank.total_clips, bank.min_clips, bank.max_clips, bank.dim, eps, bank.id_base,
-                                      int(vid_base), cand_off.data_ptr(), _ptr(cand_vid) if nnz else 0, nnz, int(max_list), lv, k,
+    workspace = _workspace(workspace, nbytes, Q.device)
+    _check(lib().vfr_score_subset_f32(*_bank_args(Q, bank, eps), int(vid_base), cand_off.data_ptr(), _ptr(cand_vid) if nnz else 0, nnz,
+                                      int(max_list), lv, k,
                                       _ptr(od), _ptr(oi), R, _ptr(rank_dist), _ptr(rank_idx), _ptr(count_lt), _ptr(bad),
                                       workspace.data_ptr(), nbytes, _stream()), "vfr_score_subset_f32")
     return od, oi, count_lt
@@ -616,28 +633,19 @@ def score_sentences(S: torch.Tensor, bank: VideoBank, probes: torch.Tensor, k: i
     if S.dim() != 2 or S.shape[1] != bank.dim:
         raise RuntimeError(f"score_sentences: S must be [Ns, {bank.dim}], got {tuple(S.shape)}")
     Ns, Nm = int(S.shape[0]), int(probes.shape[0])
-    R = 0
-    if rank_dist is not None:
-        rank_dist = _dev(rank_dist, torch.float32, "rank_dist").reshape(-1, Nm)
-        rank_idx = _dev(rank_idx, torch.int64, "rank_idx").reshape(-1, Nm)
-        R = rank_dist.shape[0]
-        if count_lt is None:
-            count_lt = torch.zeros((R, Nm), dtype=torch.int64, device=S.device)
-        count_lt = _dev(count_lt, torch.int64, "count_lt")
+    rank_dist, rank_idx, count_lt, R = _rank_keys(rank_dist, rank_idx, count_lt, Nm, S.device)
     if bad is not None:
         bad = _dev(bad, torch.int32, "bad")
     order = torch.sort(probes[:, 0], stable=True).indices if Nm > 1 else None
     sp = probes if order is None else probes[order].contiguous()
-    od = torch.empty((Nm, k), dtype=torch.float32, device=S.device) if k > 0 else None
-    oi = torch.empty((Nm, k), dtype=torch.int64, device=S.device) if k > 0 else None
+    od, oi = _out_lists(Nm, k, S.device)
     rd = ri = cl = None
     if R:
         rd = rank_dist if order is None else rank_dist[:, order].contiguous()
         ri = rank_idx if order is None else rank_idx[:, order].contiguous()
         cl = count_lt if order is None else torch.zeros_like(count_lt)
     nbytes = lib().vfr_score_sentences_workspace_bytes(Nm, Ns, k)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=S.device)
+    workspace = _workspace(workspace, nbytes, S.device)
     _check(lib().vfr_score_sentences_f32(_ptr(S) if Ns else 0, Ns, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.num_videos,
                                          bank.total_clips, bank.max_clips, bank.dim, eps, _ptr(sp) if Nm else 0, Nm, int(vid_base),
                                          int(sent_base), k, _ptr(od), _ptr(oi), R, _ptr(rd), _ptr(ri), _ptr(cl), _ptr(bad),
@@ -682,9 +690,8 @@ def topk_workspace(Nq: int, num_videos: int, k: int, device, total_clips: int | 
     """Workspace large enough for every scoring mode of a bank of ``num_videos`` videos / ``total_clips`` clips
     (64 clips per video assumed when not given)."""
     total_clips = int(total_clips) if total_clips is not None else 64 * num_videos
-    n = max(lib().vfr_score_topk_workspace_bytes(Nq, num_videos, k),
-            lib().vfr_score_topk_mfma_workspace_bytes(Nq, num_videos, total_clips, k), 1)
-    return torch.empty((n,), dtype=torch.uint8, device=device)
+    return _workspace(None, max(lib().vfr_score_topk_workspace_bytes(Nq, num_videos, k),
+                                lib().vfr_score_topk_mfma_workspace_bytes(Nq, num_videos, total_clips, k)), device)
 
 
 def topk_merge(part_dist: torch.Tensor, part_idx: torch.Tensor):
@@ -726,39 +733,39 @@ def topk_merge_keys(part_keys: torch.Tensor, want_lists: bool = True, want_keys:
     return od, oi, ok
 
 
-def gt_best_keys(own_scores: torch.Tensor, labels: torch.Tensor, id_base: torch.Tensor, sel: torch.Tensor, Nq: int):
-    """own_scores [n_sel, Ms] (``score_own``), labels bool/uint8 [R, n_sel, Ml], id_base / sel int64 [n_sel] ->
-    keys int64 [R, Nq]: best positive (score, id) per threshold and query, KEY_EMPTY elsewhere."""
+def _gt_key_args(own_scores, labels, id_base, sel, Nq: int, who: str):
+    """The checked inputs ``gt_best_keys`` / ``gt_rank_keys`` share -> (their leading arguments, R, device, the tensors the
+    pointers belong to: held by the caller until its call is queued)."""
     sc = _dev(own_scores, torch.float32, "own_scores")
     lab = labels.view(torch.uint8) if labels.dtype == torch.bool else labels
     lab = _dev(lab, torch.uint8, "labels")
     base, sel = _dev(id_base, torch.int64, "id_base"), _dev(sel, torch.int64, "sel")
     R, n_sel, Ml = lab.shape
     if sc.shape[0] != n_sel or base.numel() != n_sel or sel.numel() != n_sel:
-        raise RuntimeError("gt_best_keys: inconsistent shapes")
-    keys = torch.empty((R, Nq), dtype=torch.int64, device=sc.device)
-    _check(lib().vfr_gt_best_keys_f32(sc.data_ptr(), n_sel, min(sc.shape[1], Ml), sc.shape[1], lab.data_ptr(), R, Ml,
-                                      base.data_ptr(), sel.data_ptr(), Nq, keys.data_ptr(), _stream()), "vfr_gt_best_keys_f32")
+        raise RuntimeError(f"{who}: inconsistent shapes")
+    args = (sc.data_ptr(), n_sel, min(sc.shape[1], Ml), sc.shape[1], lab.data_ptr(), R, Ml, base.data_ptr(), sel.data_ptr(), Nq)
+    return args, R, sc.device, (sc, lab, base, sel)
+
+
+def gt_best_keys(own_scores: torch.Tensor, labels: torch.Tensor, id_base: torch.Tensor, sel: torch.Tensor, Nq: int):
+    """own_scores [n_sel, Ms] (``score_own``), labels bool/uint8 [R, n_sel, Ml], id_base / sel int64 [n_sel] ->
+    keys int64 [R, Nq]: best positive (score, id) per threshold and query, KEY_EMPTY elsewhere."""
+    args, R, device, _held = _gt_key_args(own_scores, labels, id_base, sel, Nq, "gt_best_keys")
+    keys = torch.empty((R, Nq), dtype=torch.int64, device=device)
+    _check(lib().vfr_gt_best_keys_f32(*args, keys.data_ptr(), _stream()), "vfr_gt_best_keys_f32")
     return keys
 
 
 def gt_rank_keys(own_scores: torch.Tensor, labels: torch.Tensor, id_base: torch.Tensor, sel: torch.Tensor, Nq: int):
     """``gt_best_keys`` plus, from the same two launches: the keys unpacked as (rank_dist f32 [R, Nq], rank_idx int64 [R, Nq]), a
     zeroed count buffer int64 [R, Nq] and the device flag (int32 [1]) "some selected query has no positive moment"."""
-    sc = _dev(own_scores, torch.float32, "own_scores")
-    lab = labels.view(torch.uint8) if labels.dtype == torch.bool else labels
-    lab = _dev(lab, torch.uint8, "labels")
-    base, sel = _dev(id_base, torch.int64, "id_base"), _dev(sel, torch.int64, "sel")
-    R, n_sel, Ml = lab.shape
-    if sc.shape[0] != n_sel or base.numel() != n_sel or sel.numel() != n_sel:
-        raise RuntimeError("gt_rank_keys: inconsistent shapes")
-    keys = torch.empty((R, Nq), dtype=torch.int64, device=sc.device)
-    rd = torch.empty((R, Nq), dtype=torch.float32, device=sc.device)
-    ri = torch.empty((R, Nq), dtype=torch.int64, device=sc.device)
-    cnt = torch.empty((R, Nq), dtype=torch.int64, device=sc.device)
-    missing = torch.empty((1,), dtype=torch.int32, device=sc.device)
-    _check(lib().vfr_gt_rank_keys_f32(sc.data_ptr(), n_sel, min(sc.shape[1], Ml), sc.shape[1], lab.data_ptr(), R, Ml, base.data_ptr(),
-                                      sel.data_ptr(), Nq, keys.data_ptr(), rd.data_ptr(), ri.data_ptr(), cnt.data_ptr(), missing.data_ptr(),
+    args, R, device, _held = _gt_key_args(own_scores, labels, id_base, sel, Nq, "gt_rank_keys")
+    keys = torch.empty((R, Nq), dtype=torch.int64, device=device)
+    rd = torch.empty((R, Nq), dtype=torch.float32, device=device)
+    ri = torch.empty((R, Nq), dtype=torch.int64, device=device)
+    cnt = torch.empty((R, Nq), dtype=torch.int64, device=device)
+    missing = torch.empty((1,), dtype=torch.int32, device=device)
+    _check(lib().vfr_gt_rank_keys_f32(*args, keys.data_ptr(), rd.data_ptr(), ri.data_ptr(), cnt.data_ptr(), missing.data_ptr(),
                                       _stream()), "vfr_gt_rank_keys_f32")
     return keys, rd, ri, cnt, missing
 
@@ -822,7 +829,7 @@ def vgg_fc7(frames_thwc, cfg, conv_w, conv_b, fc6, fc7) -> torch.Tensor:
     fc_dim = f6w.shape[0]
     out = torch.empty((T, fc_dim), dtype=torch.float32, device=fr.device)
     nbytes = lib().vfr_vgg_fc7_workspace_bytes(T, H, W, ctypes.cast(cfg_i, ctypes.c_void_p), len(cfg), fc_dim)
-    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=fr.device)
+    ws = _workspace(None, nbytes, fr.device)
     _check(lib().vfr_vgg_fc7_f32(fr.data_ptr(), T, H, W, ctypes.cast(cfg_i, ctypes.c_void_p), len(cfg),
                                  ctypes.cast(wp, ctypes.c_void_p), ctypes.cast(bp, ctypes.c_void_p), f6w.data_ptr(),
                                  f6b.data_ptr(), f7w.data_ptr(), f7b.data_ptr(), fc_dim, out.data_ptr(), ws.data_ptr(),
@@ -883,14 +890,14 @@ def resnet_pool(frames_thwc, packed, blocks=RESNET152_BLOCKS, width: int = 64, e
     bp = (ctypes.c_void_p * nconv)(*[b.data_ptr() for b in bns])
     out = torch.empty((T, 32 * width), dtype=torch.float32, device=fr.device)
     nbytes = lib().vfr_resnet_pool_workspace_bytes(T, H, W, ctypes.cast(bl, ctypes.c_void_p), width)
-    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=fr.device)
+    ws = _workspace(None, nbytes, fr.device)
     if isinstance(packed, ResnetPacked):
         # the model's weights folded once (BatchNorm into the convolutions, tap-major), reused by every later call
         key = (tuple(int(b) for b in blocks), int(width), float(eps), fr.device)
         folded = packed.folded.get(key)
         if folded is None:
             fb = lib().vfr_resnet_folded_bytes(ctypes.cast(bl, ctypes.c_void_p), width)
-            folded = torch.empty((max(fb, 1),), dtype=torch.uint8, device=fr.device)
+            folded = _workspace(None, fb, fr.device)
             _check(lib().vfr_resnet_fold_f32(ctypes.cast(bl, ctypes.c_void_p), width, ctypes.cast(wp, ctypes.c_void_p),
                                              ctypes.cast(bp, ctypes.c_void_p), eps, folded.data_ptr(), folded.numel(), _stream()),
                    "vfr_resnet_fold_f32")
@@ -960,7 +967,7 @@ def bilstm_train_backward(gout, gates, cs, whhT_f, whhT_b):
     _, T, B, G = gates.shape
     H = G // 4
     nbytes = lib().vfr_bilstm_train_backward_workspace_bytes(B, H)
-    wsb = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=gout.device)
+    wsb = _workspace(None, nbytes, gout.device)
     dpre = torch.empty_like(gates)
     _check(lib().vfr_bilstm_train_backward_f32(gout.data_ptr(), gates.data_ptr(), cs.data_ptr(), whhT_f.data_ptr(), whhT_b.data_ptr(),
                                                B, T, H, dpre.data_ptr(), wsb.data_ptr(), nbytes, _stream()),
@@ -975,7 +982,7 @@ def ranking_loss_forward(posit, intra, inter, lang, maskp, maskn, n_samples: int
     maskp, maskn = _dev(maskp, torch.int64, "maskp"), _dev(maskn, torch.int64, "maskn")
     P, Nn, D = posit.shape[0], intra.shape[0], posit.shape[1]
     nbytes = lib().vfr_ranking_loss_workspace_bytes(P, Nn, n_samples)
-    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=posit.device)
+    ws = _workspace(None, nbytes, posit.device)
     loss = torch.empty((1,), dtype=torch.float32, device=posit.device)
     _check(lib().vfr_ranking_loss_f32(posit.data_ptr(), intra.data_ptr(), inter.data_ptr(), lang.data_ptr(), maskp.data_ptr(),
                                       maskn.data_ptr(), P, Nn, n_samples, D, b, lamb, eps, loss.data_ptr(), ws.data_ptr(),

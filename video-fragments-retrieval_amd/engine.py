@@ -20,9 +20,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from ._vfr import KEY_EMPTY as KEY_INF, csr_offsets   # (does not load libvfr.so)  KEY_INF = key of (+inf, max id): "no positive moment here"
 from .utils import generate_moments, get_iou
-
-KEY_INF = (0x7F800000 << 32) | 0xFFFFFFFF      # key of (+inf, max id): "no ground-truth-positive moment here"
 
 
 class HipOps:
@@ -33,6 +32,10 @@ class HipOps:
         _vfr.lib()
         self.v = _vfr
         self.score_mode = score_mode          # None: _vfr.DEFAULT_SCORE_MODE ("mfma": MFMA pre-filter, exact results)
+
+    def _video_mode(self):
+        """Mode of the video-level kernels, which have no approximate form: "bf16" gets their default."""
+        return None if self.score_mode == "bf16" else self.score_mode
 
     def make_bank(self, emb, clip_off, id_base):
         return self.v.VideoBank(emb, clip_off, id_base)
@@ -51,12 +54,10 @@ class HipOps:
                                  thr_seed=thr_seed, mode=self.score_mode)
 
     def score_video_topk(self, Q, bank, k, own_dist=None, own_idx=None, count=None, workspace=None):
-        return self.v.score_video_topk(Q, bank, k, own_dist, own_idx, count=count, workspace=workspace,
-                                       mode=None if self.score_mode == "bf16" else self.score_mode)
+        return self.v.score_video_topk(Q, bank, k, own_dist, own_idx, count=count, workspace=workspace, mode=self._video_mode())
 
     def score_moment_nms(self, Q, bank, k, per_video=0, nms_iou=1.0, workspace=None):
-        return self.v.score_moment_nms(Q, bank, k, per_video, nms_iou, workspace=workspace,
-                                       mode=None if self.score_mode == "bf16" else self.score_mode)
+        return self.v.score_moment_nms(Q, bank, k, per_video, nms_iou, workspace=workspace, mode=self._video_mode())
 
     def score_subset(self, Q, bank, cand_off, cand_vid, k, level="moments", vid_base=0, rank_dist=None, rank_idx=None, count_lt=None,
                      workspace=None, bad=None, max_list=None):
@@ -185,7 +186,7 @@ def build_corpus(model, feature_bank, device, ops=None, rank=0, world=1) -> Corp
     ops = ops or HipOps()
     off_all = feature_bank.clip_off.cpu().numpy().astype(np.int64)
     counts = np.diff(off_all)
-    mom_off_all = np.concatenate([[0], np.cumsum(counts * (counts + 1) // 2)]).astype(np.int64)
+    mom_off_all = csr_offsets(counts)[1]
     lo, hi = shard_range(len(counts), rank, world)
     c0, c1 = int(off_all[lo]), int(off_all[hi])
     clip_off = torch.from_numpy((off_all[lo:hi + 1] - c0).astype(np.int32)).to(device)
@@ -250,7 +251,21 @@ def encode_clips_streamed(ops, model, seg, ctx, off, device, chunk_clips=None):
 
 
 _SIDE_STREAMS = {}
-_TLS = __import__("threading").local()          # per-thread pinned flag words (one per device)
+_TLS = __import__("threading").local()          # per-thread pinned flag words (one per device and dtype)
+
+
+def _pinned_flag(device, dtype=torch.int32):
+    """This thread's page-locked [1] word the "no positive moment" flag of a pass on ``device`` is copied to."""
+    flags = _TLS.__dict__.setdefault("flags", {})
+    flag = flags.get((device, dtype))
+    if flag is None:
+        flag = flags[(device, dtype)] = torch.zeros((1,), dtype=dtype).pin_memory()
+    return flag
+
+
+def raise_no_positive():
+    """What ``np.where(...)[0][0]`` raises in the reference (``evaluate.py:77``, Q3) for a query without a positive moment."""
+    raise IndexError("index 0 is out of bounds for axis 0 with size 0 (no ground-truth-positive moment)")
 
 
 def overlapped(device, main_fn, side_fn, enable=True):
@@ -282,8 +297,7 @@ def corpus_from_embeddings(emb, counts, device, ops=None, rank=0, world=1) -> Co
     """Same, from precomputed clip embeddings [sum n, D] of the whole corpus (per-item iterator API)."""
     ops = ops or HipOps()
     counts = np.asarray(counts, np.int64)
-    off_all = np.concatenate([[0], np.cumsum(counts)])
-    mom_off_all = np.concatenate([[0], np.cumsum(counts * (counts + 1) // 2)]).astype(np.int64)
+    off_all, mom_off_all = csr_offsets(counts)
     lo, hi = shard_range(len(counts), rank, world)
     c0, c1 = int(off_all[lo]), int(off_all[hi])
     clip_off = torch.from_numpy((off_all[lo:hi + 1] - c0).astype(np.int32)).to(device)
@@ -457,11 +471,25 @@ def best_positive_keys(shard: CorpusShard, Q, gt: QueryGT, ops, world=1, reduce=
     return keys
 
 
+def _single_shard_pass(ops, bank, Q, gt: QueryGT, k, workspace, flag, landed=None):
+    """One shard, one IoU pair, a ROCm device: own-video scores, then keys + their rank-key form + the zeroed count buffer + the
+    "no positive moment" flag from the same two launches (vfr_gt_rank_keys_f32), the flag on its way to the page-locked
+    ``flag`` (``landed``, outside a graph capture only: the event the host waits on instead of the scoring), then the fused pass.
+    Device work on the current stream only -- this is also the body a HIP graph captures.  Returns (counts, dist, idx)."""
+    sc = ops.score_own(Q, bank, gt.own_local)
+    _keys, rank_dist, rank_idx, counts0, missing = ops.gt_rank_keys(sc, gt.labels, gt.base, gt.sel, gt.num_queries)
+    flag.copy_(missing, non_blocking=True)
+    if landed is not None:
+        landed.record()
+    od, oi, counts = ops.score_topk(Q, bank, k, rank_dist, rank_idx, workspace=workspace, count_lt=counts0)
+    return counts, od, oi
+
+
 def corpus_ranks(shard: CorpusShard, Q, own_global, labels, ops=None, k=0, world=1, workspace=None, gt=None):
     """The fused pass.  Returns (ranks [R, Nq] int64 = 0-based position of the best GT-positive moment in the
     global (score, id) order -- ``evaluate.py:77``'s MR --, top-k (dist, idx) or (None, None)).
 
-    Raises IndexError when some query has no ground-truth-positive moment, like ``np.where(...)[0][0]`` does
+    Raises IndexError (``raise_no_positive``) when some query has no positive moment, like ``np.where(...)[0][0]`` does
     in the reference (Q3)."""
     ops = ops or HipOps()
     gt = gt if gt is not None else prepare_gt(shard, own_global, labels)
@@ -469,24 +497,15 @@ def corpus_ranks(shard: CorpusShard, Q, own_global, labels, ops=None, k=0, world
     state = {}
     if (_group(world) is None and gt.num_thresholds == 2 and gt.sel is not None and gt.all_local and hasattr(ops, "gt_rank_keys")
             and Q.is_cuda):
-        # one shard, one IoU pair, a ROCm device (a serving request, the single-GPU bench step): keys, their unpacked rank-key
-        # form, the zeroed count buffer and the "no positive moment" flag come out of the same two launches
-        # (vfr_gt_rank_keys_f32) instead of seven small torch kernels behind them -- ~40 us of a 0.26 ms single-query request
-        sc = ops.score_own(Q, shard.bank, gt.own_local)
-        _keys, rank_dist, rank_idx, counts0, missing = ops.gt_rank_keys(sc, gt.labels, gt.base, gt.sel, gt.num_queries)
-        flags = _TLS.__dict__.setdefault("iflags", {})
-        flag = flags.get(Q.device)
-        if flag is None:
-            flag = flags[Q.device] = torch.zeros((1,), dtype=torch.int32).pin_memory()
-        flag.copy_(missing, non_blocking=True)
-        landed = torch.cuda.Event()
-        landed.record()
-        od, oi, counts = ops.score_topk(Q, shard.bank, k, rank_dist, rank_idx, workspace=workspace, count_lt=counts0)
+        # a serving request, the single-GPU bench step: two launches instead of the keys and seven small torch kernels behind
+        # them -- ~40 us of a 0.26 ms single-query request
+        flag, landed = _pinned_flag(Q.device), torch.cuda.Event()
+        out = _single_shard_pass(ops, shard.bank, Q, gt, k, workspace, flag, landed)
         landed.synchronize()
         getattr(ops, "poll_faults", int)()
         if int(flag[0]):
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (no ground-truth-positive moment)")
-        return counts, od, oi
+            raise_no_positive()
+        return out
     keys = best_positive_keys(shard, Q, gt, ops, world, reduce=not fused)
 
     def watch(keys_global):
@@ -496,12 +515,8 @@ def corpus_ranks(shard: CorpusShard, Q, own_global, labels, ops=None, k=0, world
         state["missing"] = (keys_global == KEY_INF).any()
         state["async"] = keys_global.is_cuda
         if state["async"]:
-            flags = _TLS.__dict__.setdefault("flags", {})
-            flag = flags.get(keys_global.device)
-            if flag is None:
-                flag = flags[keys_global.device] = torch.empty((), dtype=torch.bool).pin_memory()
-            flag.copy_(state["missing"], non_blocking=True)
-            state["flag"] = flag
+            state["flag"] = _pinned_flag(keys_global.device, torch.bool)
+            state["flag"].copy_(state["missing"], non_blocking=True)
             state["landed"] = torch.cuda.Event()
             state["landed"].record()
 
@@ -510,7 +525,7 @@ def corpus_ranks(shard: CorpusShard, Q, own_global, labels, ops=None, k=0, world
             state["landed"].synchronize()
             getattr(ops, "poll_faults", int)()       # the query encoder finished before the keys: a give-up of its sequence kernel is known by now
         if bool(state["flag"] if state["async"] else state["missing"]):
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (no ground-truth-positive moment)")
+            raise_no_positive()
     if fused:
         # three collectives per pass instead of five: the best-GT keys ride on the sample exchange, the rank counts on the
         # final one (sharded_search_fused)
@@ -549,7 +564,7 @@ class GraphedRequest:
     request into the static input buffers and ``replay``.  Everything inside the capture is device work on the capture
     stream through the same C-ABI calls as the eager path (same kernels, same bits: GPU test); the library's
     bank-side products are guarded on the device (VFR_MFMA_BANK_READY is re-verified by hash inside every replay), so a bank
-    rewritten between replays costs a recomputation, never a wrong result.  The "no ground-truth-positive moment" flag
+    rewritten between replays costs a recomputation, never a wrong result.  The "no positive moment" flag
     (``evaluate.py:77``'s IndexError) travels to page-locked memory inside the graph and is read by ``check`` after the
     caller's synchronisation.  Single shard (world == 1); the query count, token length, annotator capacity and k are fixed
     at construction -- build one instance per served batch shape."""
@@ -587,11 +602,7 @@ class GraphedRequest:
         Q = ops.encode_queries(self.model, self.tokens)
         labels = ops.gt_labels((self.times, self.nannot), self.n_own, self.thresholds, self.strict, shard.device, Mmax=self.Mmax)
         gt = QueryGT(len(self.thresholds), self.num_queries, self.sel, self.own_local, labels, self.base, True, self.Mmax)
-        sc = ops.score_own(Q, shard.bank, gt.own_local)
-        _keys, rank_dist, rank_idx, counts0, missing = ops.gt_rank_keys(sc, gt.labels, gt.base, gt.sel, gt.num_queries)
-        self.flag.copy_(missing, non_blocking=True)
-        od, oi, counts = ops.score_topk(Q, shard.bank, self.k, rank_dist, rank_idx, workspace=self.workspace, count_lt=counts0)
-        return counts, od, oi
+        return _single_shard_pass(ops, shard.bank, Q, gt, self.k, self.workspace, self.flag)
 
     def load(self, tokens, times, own_global):
         """The request into the static buffers (asynchronous copies on the current stream, from page-locked staging):
@@ -637,7 +648,7 @@ class GraphedRequest:
         report device-side recoveries (``_vfr.poll_faults``)."""
         getattr(self.ops, "poll_faults", int)()
         if int(self.flag[0]):
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (no ground-truth-positive moment)")
+            raise_no_positive()
 
 
 def corpus_topk(shard: CorpusShard, Q, k, ops=None, world=1, workspace=None):
@@ -676,15 +687,21 @@ def corpus_video_topk(shard: CorpusShard, Q, k, own_global=None, ops=None, world
     if own_global is not None:
         own_d, own_i = _unpack_key(own_best_keys(shard, Q, own_global, ops, world))
         own_d, own_i = own_d.contiguous(), own_i.contiguous()
-    od, oi, cnt = ops.score_video_topk(Q, shard.bank, k, own_d, own_i, workspace=workspace)
+    od, oi, cnt = _exchange(*ops.score_video_topk(Q, shard.bank, k, own_d, own_i, workspace=workspace), k, ops, world)
+    vid = _video_of(shard, oi) if k > 0 else None
+    return od, oi, vid, cnt
+
+
+def _exchange(od, oi, cnt, k, ops, world):
+    """The sharded tail of a retrieval variant: the per-shard lists merged (one packed all_gather, k > 0), then the counts
+    summed (one all_reduce, when there are counts) -- in this order on every rank.  One shard: nothing to do."""
     dist = _group(world)
     if dist is not None:
         if k > 0:
             od, oi = gather_merge_topk(od, oi, ops, world)
         if cnt is not None:
             dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
-    vid = _video_of(shard, oi) if k > 0 else None
-    return od, oi, vid, cnt
+    return od, oi, cnt
 
 
 def _video_of(shard: CorpusShard, oi):
@@ -700,9 +717,7 @@ def corpus_moment_nms(shard: CorpusShard, Q, k, per_video=0, nms_iou=1.0, ops=No
     a video and a video never spans shards, so the per-shard lists merge with the moment-key merge.
     Returns (dist [Nq,k], moment id [Nq,k] int64, video index [Nq,k] int64 (-1 = padding)); the ids feed ``video_results``."""
     ops = ops or HipOps()
-    od, oi = ops.score_moment_nms(Q, shard.bank, k, per_video, nms_iou, workspace=workspace)
-    if k > 0 and _group(world) is not None:
-        od, oi = gather_merge_topk(od, oi, ops, world)
+    od, oi, _ = _exchange(*ops.score_moment_nms(Q, shard.bank, k, per_video, nms_iou, workspace=workspace), None, k, ops, world)
     return od, oi, _video_of(shard, oi)
 
 
@@ -785,14 +800,8 @@ def corpus_subset_topk(shard: CorpusShard, Q, k, lists: CandidateLists, level="m
         rd, ri = _unpack_key(rank_keys)
         rd, ri = rd.contiguous(), ri.contiguous()
     off_t, vid_t = lists.on(shard.device)
-    od, oi, cnt = ops.score_subset(Q, shard.bank, off_t, vid_t, k, level, shard.lo, rd, ri, workspace=workspace,
-                                   max_list=lists.max_list)
-    dist = _group(world)
-    if dist is not None:
-        if k > 0:
-            od, oi = gather_merge_topk(od, oi, ops, world)
-        if cnt is not None:
-            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+    od, oi, cnt = _exchange(*ops.score_subset(Q, shard.bank, off_t, vid_t, k, level, shard.lo, rd, ri, workspace=workspace,
+                                              max_list=lists.max_list), k, ops, world)
     vid = _video_of(shard, oi) if k > 0 else None
     if cnt is not None and squeeze:
         cnt = cnt[0]
@@ -832,13 +841,7 @@ def corpus_sentence_topk(shard: CorpusShard, S, probes, k, own_sentence=None, op
             col = np.where(ss == es, ss, ns + (ss * (2 * ns - ss - 1)) // 2 + (es - ss - 1))     # utils.generate_moments position
             rd[sel_t] = sc[torch.arange(len(sel), device=sc.device), torch.from_numpy(col).to(sc.device)]
     probes_t = torch.from_numpy(pr.astype(np.int32)).to(shard.device)
-    od, oi, cnt = ops.score_sentences(S, shard.bank, probes_t, k, shard.lo, 0, rd, ri, workspace=workspace)
-    dist = _group(world)
-    if dist is not None:
-        if k > 0:
-            od, oi = gather_merge_topk(od, oi, ops, world)
-        if cnt is not None:
-            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+    od, oi, cnt = _exchange(*ops.score_sentences(S, shard.bank, probes_t, k, shard.lo, 0, rd, ri, workspace=workspace), k, ops, world)
     return od, oi, (cnt[0] if cnt is not None else None)
 
 
@@ -1024,66 +1027,66 @@ class TorchCpuOps:
             out[q, :sc.numel()] = sc
         return out
 
+    def _dense_keys(self, Q, bank):
+        """[Nq, M] packed (score, global id) keys of every moment of the bank."""
+        sc = self._dense(Q, bank)
+        return _pack_key(sc, (bank.id_base + torch.arange(sc.shape[1]))[None, :].expand_as(sc))
+
+    @staticmethod
+    def _pad_k(srt, k):
+        """Keys padded with KEY_INF to k along the last axis."""
+        pad = k - srt.shape[-1]
+        return srt if pad <= 0 else torch.cat([srt, torch.full(tuple(srt.shape[:-1]) + (pad,), KEY_INF, dtype=torch.int64)], dim=-1)
+
+    @staticmethod
+    def _lists_of(keys):
+        """Keys -> (dist, idx) lists, KEY_INF as the padding (+inf, -1)."""
+        od, oi = _unpack_key(keys)
+        return torch.where(keys == KEY_INF, torch.full_like(od, float("inf")), od), torch.where(keys == KEY_INF, torch.full_like(oi, -1), oi)
+
+    @classmethod
+    def _topk_lists(cls, keys, k):
+        """The k smallest keys per row of ``keys`` [N, M] as padded lists; (None, None) for k == 0."""
+        return cls._lists_of(cls._pad_k(keys.sort(dim=1).values[:, :k], k)) if k > 0 else (None, None)
+
+    @staticmethod
+    def _counts_below(keys, kstar, count_lt):
+        """[R, N] = per packed rank key ``kstar`` [R, N] the keys of its row of ``keys`` [N, M] that sort strictly before it, plus
+        ``count_lt``; None without rank keys."""
+        if kstar is None:
+            return None
+        counts = (keys[None, :, :] < kstar[:, :, None]).sum(-1)
+        return counts if count_lt is None else counts + count_lt
+
     def slice_bank(self, bank, counts, v0, v1):
-        counts = np.asarray(counts, np.int64)
-        off = np.concatenate([[0], np.cumsum(counts)])
-        mom = np.concatenate([[0], np.cumsum(counts * (counts + 1) // 2)])
+        off, mom = csr_offsets(counts)
         clip_off = torch.from_numpy((off[v0:v1 + 1] - off[v0]).astype(np.int32))
         return TorchCpuOps.Bank(bank.emb[int(off[v0]):int(off[v1])], clip_off, bank.id_base + int(mom[v0]))
 
     def score_topk(self, Q, bank, k, rank_dist, rank_idx, workspace=None, count_lt=None, thr_seed=None):
-        sc = self._dense(Q, bank)            # thr_seed is only an accelerator: the exact result does not depend on it
-        ids = bank.id_base + torch.arange(sc.shape[1])
-        keys = _pack_key(sc, ids[None, :].expand_as(sc))
-        counts = None
-        if rank_dist is not None:
-            kstar = _pack_key(rank_dist.reshape(-1, Q.shape[0]), rank_idx.reshape(-1, Q.shape[0]))
-            counts = (keys[None, :, :] < kstar[:, :, None]).sum(-1)
-            if count_lt is not None:
-                counts = counts + count_lt
-        od = oi = None
-        if k > 0:
-            srt = keys.sort(dim=1).values[:, :k]
-            pad = k - srt.shape[1]
-            if pad > 0:
-                srt = torch.cat([srt, torch.full((srt.shape[0], pad), KEY_INF, dtype=torch.int64)], dim=1)
-            od, oi = _unpack_key(srt)
-            od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
-            oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
-        return od, oi, counts
+        keys = self._dense_keys(Q, bank)     # thr_seed is only an accelerator: the exact result does not depend on it
+        kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Q.shape[0]), rank_idx.reshape(-1, Q.shape[0]))
+        return self._topk_lists(keys, k) + (self._counts_below(keys, kstar, count_lt),)
 
     def score_video_topk(self, Q, bank, k, own_dist=None, own_idx=None, count=None, workspace=None):
         """Video-level retrieval from the dense scores: per video the smallest (score, id) key, then the k smallest of those
         and the number of videos below the own key (same semantics as ``_vfr.score_video_topk``)."""
-        sc = self._dense(Q, bank)
+        keys = self._dense_keys(Q, bank)
         Nq = Q.shape[0]
-        keys = _pack_key(sc, (bank.id_base + torch.arange(sc.shape[1]))[None, :].expand_as(sc))
-        n = torch.tensor(bank.counts, dtype=torch.int64)
-        m = n * (n + 1) // 2
-        best = [keys[:, int(a):int(b)].min(dim=1).values for a, b in zip(m.cumsum(0) - m, m.cumsum(0)) if b > a]
+        mo = csr_offsets(bank.counts)[1]
+        best = [keys[:, int(a):int(b)].min(dim=1).values for a, b in zip(mo[:-1], mo[1:]) if b > a]
         best = torch.stack(best, dim=1) if best else torch.zeros((Nq, 0), dtype=torch.int64)
-        if own_dist is not None:
-            own = _pack_key(own_dist.reshape(Nq), own_idx.reshape(Nq))
-            c = (best < own[:, None]).sum(dim=1)
-            count = c if count is None else count + c
-        od = oi = None
-        if k > 0:
-            srt = best.sort(dim=1).values[:, :k]
-            if srt.shape[1] < k:
-                srt = torch.cat([srt, torch.full((Nq, k - srt.shape[1]), KEY_INF, dtype=torch.int64)], dim=1)
-            od, oi = _unpack_key(srt)
-            od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
-            oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
-        return od, oi, count
+        if own_dist is not None:             # one key per query, [Nq] counts
+            count = self._counts_below(best, _pack_key(own_dist.reshape(1, Nq), own_idx.reshape(1, Nq)), count)[0]
+        return self._topk_lists(best, k) + (count,)
 
     def score_moment_nms(self, Q, bank, k, per_video=0, nms_iou=1.0, workspace=None):
         """Diversified moment retrieval from the dense scores (same rule as ``_vfr.score_moment_nms``): per video, moments in
         key order, greedy acceptance under the float64 IoU test and the cap, then the k smallest accepted keys."""
-        sc = self._dense(Q, bank)
+        keys = self._dense_keys(Q, bank)
         Nq = Q.shape[0]
-        keys = _pack_key(sc, (bank.id_base + torch.arange(sc.shape[1]))[None, :].expand_as(sc))
         acc = torch.full_like(keys, KEY_INF)
-        cap = per_video if per_video > 0 else sc.shape[1] + 1
+        cap = per_video if per_video > 0 else keys.shape[1] + 1
         m0 = 0
         for n in bank.counts:
             spans = np.asarray(generate_moments(int(n)), np.int64).reshape(-1, 2)
@@ -1106,13 +1109,7 @@ class TorchCpuOps:
                 taken += take.long()
                 acc[rows[take], m0 + j[take]] = kv[rows[take], j[take]]
             m0 += M
-        srt = acc.sort(dim=1).values[:, :k]
-        if srt.shape[1] < k:
-            srt = torch.cat([srt, torch.full((Nq, k - srt.shape[1]), KEY_INF, dtype=torch.int64)], dim=1)
-        od, oi = _unpack_key(srt)
-        od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
-        oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
-        return od, oi
+        return self._lists_of(self._pad_k(acc.sort(dim=1).values[:, :k], k))
 
     def score_subset(self, Q, bank, cand_off, cand_vid, k, level="moments", vid_base=0, rank_dist=None, rank_idx=None, count_lt=None,
                      workspace=None, bad=None, max_list=None):
@@ -1120,19 +1117,13 @@ class TorchCpuOps:
         the listed videos of this bank (moments, or each video's smallest key), the k smallest, and the keys below each rank key."""
         if level not in ("moments", "videos"):
             raise RuntimeError(f"score_subset: unknown level {level!r} (moments, videos)")
-        sc = self._dense(Q, bank)
+        keys = self._dense_keys(Q, bank)
         Nq = Q.shape[0]
-        keys = _pack_key(sc, (bank.id_base + torch.arange(sc.shape[1]))[None, :].expand_as(sc))
         n = np.asarray(bank.counts, np.int64)
         Nv = len(n)
-        mo = np.concatenate([[0], np.cumsum(n * (n + 1) // 2)]).astype(np.int64)
+        mo = csr_offsets(n)[1]
         off = [int(x) for x in torch.as_tensor(cand_off).tolist()]
         vid = [int(x) for x in torch.as_tensor(cand_vid).tolist()]
-        kstar = None
-        if rank_dist is not None:
-            kstar = _pack_key(rank_dist.reshape(-1, Nq).contiguous(), rank_idx.reshape(-1, Nq))
-        R = 0 if kstar is None else kstar.shape[0]
-        counts = torch.zeros((R, Nq), dtype=torch.int64)
         rows = []
         for q in range(Nq):
             sel = [v - vid_base for v in vid[off[q]:off[q + 1]] if 0 <= v - vid_base < Nv and n[v - vid_base] > 0]
@@ -1141,21 +1132,11 @@ class TorchCpuOps:
                 kk = keys[q, torch.from_numpy(cols)]
             else:
                 kk = torch.stack([keys[q, int(mo[v]):int(mo[v + 1])].min() for v in sel]) if sel else torch.zeros(0, dtype=torch.int64)
-            if R:
-                counts[:, q] = (kk[None, :] < kstar[:, q, None]).sum(dim=1)
-            srt = kk.sort().values[:k]
-            rows.append(torch.cat([srt, torch.full((k - srt.numel(),), KEY_INF, dtype=torch.int64)]))
-        od = oi = None
-        if k > 0:
-            srt = torch.stack(rows) if rows else torch.zeros((0, k), dtype=torch.int64)
-            od, oi = _unpack_key(srt)
-            od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
-            oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
-        if R == 0:
-            counts = None
-        elif count_lt is not None:
-            counts = counts + count_lt
-        return od, oi, counts
+            rows.append(kk)
+        longest = max([r.numel() for r in rows], default=0)             # each query's keys as one KEY_INF-padded row
+        sub = torch.stack([self._pad_k(r, longest) for r in rows]) if rows else torch.zeros((0, 0), dtype=torch.int64)
+        kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nq), rank_idx.reshape(-1, Nq))
+        return self._topk_lists(sub, k) + (self._counts_below(sub, kstar, count_lt),)
 
     def score_sentences(self, S, bank, probes, k, vid_base=0, sent_base=0, rank_dist=None, rank_idx=None, count_lt=None, bad=None,
                         workspace=None, eps=1e-6):
@@ -1168,13 +1149,8 @@ class TorchCpuOps:
         Nm = len(rows)
         off = bank.clip_off.tolist()
         Nv = len(off) - 1
-        kstar = None
-        if rank_dist is not None:
-            kstar = _pack_key(rank_dist.reshape(-1, Nm).contiguous(), rank_idx.reshape(-1, Nm))
-        R = 0 if kstar is None else kstar.shape[0]
-        counts = torch.zeros((R, Nm), dtype=torch.int64)
         ids = sent_base + torch.arange(Ns)
-        out = torch.full((Nm, k), KEY_INF, dtype=torch.int64)
+        out = torch.full((Nm, Ns), KEY_INF, dtype=torch.int64)          # a probe without keys here: padding, nothing below
         for m, (gv, s0, e0) in enumerate(rows):
             wrong = gv < 0 or s0 < 0 or e0 < s0
             lv = gv - vid_base
@@ -1190,30 +1166,12 @@ class TorchCpuOps:
             acc = d[:, 0]
             for c in range(1, d.shape[1]):
                 acc = acc + d[:, c]
-            keys = _pack_key(acc / float(e0 - s0 + 1), ids)
-            if R:
-                counts[:, m] = (keys[None, :] < kstar[:, m, None]).sum(dim=1)
-            srt = keys.sort().values[:k]
-            out[m, :srt.numel()] = srt
-        od = oi = None
-        if k > 0:
-            od, oi = _unpack_key(out)
-            od = torch.where(out == KEY_INF, torch.full_like(od, float("inf")), od)
-            oi = torch.where(out == KEY_INF, torch.full_like(oi, -1), oi)
-        if R == 0:
-            counts = None
-        elif count_lt is not None:
-            counts = counts + count_lt
-        return od, oi, counts
+            out[m] = _pack_key(acc / float(e0 - s0 + 1), ids)
+        kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nm), rank_idx.reshape(-1, Nm))
+        return self._topk_lists(out, k) + (self._counts_below(out, kstar, count_lt),)
 
     def topk_merge(self, part_dist, part_idx):
-        G, Nq, k = part_dist.shape
-        keys = torch.where(part_idx >= 0, _pack_key(part_dist, part_idx.clamp(min=0)), torch.full_like(part_idx, KEY_INF))
-        srt = keys.permute(1, 0, 2).reshape(Nq, G * k).sort(dim=1).values[:, :k]
-        od, oi = _unpack_key(srt)
-        od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
-        oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
-        return od, oi
+        return self.merge_keys(self.pack_keys(part_dist, part_idx))[:2]
 
     def pack_keys(self, dist_t, idx_t, out=None):
         keys = torch.where(idx_t >= 0, _pack_key(dist_t, idx_t.clamp(min=0)), torch.full_like(idx_t, KEY_INF))
@@ -1225,12 +1183,7 @@ class TorchCpuOps:
     def merge_keys(self, part_keys, want_lists=True, want_keys=False):
         G, Nq, k = part_keys.shape
         srt = part_keys.clamp(max=KEY_INF).permute(1, 0, 2).reshape(Nq, G * k).sort(dim=1).values[:, :k].contiguous()
-        od = oi = None
-        if want_lists:
-            od, oi = _unpack_key(srt)
-            od = torch.where(srt == KEY_INF, torch.full_like(od, float("inf")), od)
-            oi = torch.where(srt == KEY_INF, torch.full_like(oi, -1), oi)
-        return od, oi, (srt if want_keys else None)
+        return (self._lists_of(srt) if want_lists else (None, None)) + ((srt if want_keys else None),)
 
     def gt_labels(self, packed_times, n_own, thresholds, strict, device, Mmax=None):
         return torch.from_numpy(gt_label_table(packed_times, np.asarray(n_own), thresholds, strict))

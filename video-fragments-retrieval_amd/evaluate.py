@@ -14,6 +14,7 @@ unstable argsort leaves them unspecified); ``np.random.choice`` is drawn only wh
 """
 from __future__ import annotations
 
+import contextlib
 import itertools
 
 import numpy as np
@@ -69,25 +70,58 @@ def _encode_both(model, video_iterator, drained, tokens, device, ops, rank, worl
     return shard, names, Q
 
 
-def evaluate(model, video_iterator, lang_iterator, annotations, device, preliminary=100, model_types=['model'],
-             iou_thresholds=[0.5, 0.7], rank=0, world=1, return_topk=0):
+@contextlib.contextmanager
+def _eval_mode(model):
+    """``model.eval()`` for the block; the caller's mode comes back on EVERY way out, an exception included."""
     was_training = model.training
     model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
+
+
+def _prepare(model, video_iterator, lang_iterator, device, rank, world, query_fn=None, empty_ok=True):
+    """What every entry point starts with: the provider, both iterators drained, the clip shard and the query batch encoded
+    (``query_fn(tokens)`` instead of the model's query encoder when given), each query's global video index.
+    Returns (ops, tokens, annot_ids, shard, names, Q, own); without queries (``empty_ok``) the corpus is still embedded and
+    shard / names / Q / own are None."""
     ops = engine.ops_for(device)
     drained = _drain_videos(video_iterator)
     tokens, q_videos, annot_ids = _drain_queries(lang_iterator)
-    if not tokens:
+    if not tokens and empty_ok:
         embed_corpus(model, video_iterator, device, ops, rank, world, drained)
-        model.train(was_training)
-        return {f"{mt}, IoU={thr}": get_metrics({1: [], 10: [], 100: [], "MR": []})
-                for mt, thr in itertools.product(model_types, iou_thresholds)}
-    shard, names, Q = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world)
+        return ops, tokens, annot_ids, None, None, None, None
+    shard, names, Q = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world,
+                                   (lambda: query_fn(tokens)) if query_fn else None)
     video_index = {name: i for i, name in enumerate(names)}
     own = np.asarray([video_index[v] for v in q_videos], np.int64)
-    times = [annotations[a]["times"] for a in annot_ids]
-    labels = engine.gt_labels(times, shard.counts_all[own], list(iou_thresholds), True, shard.device, ops)   # a11, on the device
-    ranks, top_dist, top_idx = engine.corpus_ranks(shard, Q, own, labels, ops, k=return_topk, world=world)
-    ranks = ranks.cpu().numpy()
+    return ops, tokens, annot_ids, shard, names, Q, own
+
+
+def _rank_metrics(ranks, atk):
+    """0-based ranks [N] -> the recall lists ``get_metrics`` folds: hit at k per entry of ``atk``, and "MR"."""
+    rec = {k: (ranks < k).astype(int) for k in atk}
+    rec["MR"] = ranks
+    return rec
+
+
+def _empty_metrics(atk, with_mr=True):
+    """The recall lists of an empty query batch."""
+    return {k: [] for k in list(atk) + (["MR"] if with_mr else [])}
+
+
+def evaluate(model, video_iterator, lang_iterator, annotations, device, preliminary=100, model_types=['model'],
+             iou_thresholds=[0.5, 0.7], rank=0, world=1, return_topk=0):
+    with _eval_mode(model):
+        ops, _, annot_ids, shard, names, Q, own = _prepare(model, video_iterator, lang_iterator, device, rank, world)
+        if shard is None:
+            return {f"{mt}, IoU={thr}": get_metrics(_empty_metrics((1, 10, 100)))
+                    for mt, thr in itertools.product(model_types, iou_thresholds)}
+        times = [annotations[a]["times"] for a in annot_ids]
+        labels = engine.gt_labels(times, shard.counts_all[own], list(iou_thresholds), True, shard.device, ops)   # a11, on the device
+        ranks, top_dist, top_idx = engine.corpus_ranks(shard, Q, own, labels, ops, k=return_topk, world=world)
+        ranks = ranks.cpu().numpy()
 
     recalls = {}
     total = int(shard.mom_off_all[-1])
@@ -104,22 +138,19 @@ def evaluate(model, video_iterator, lang_iterator, annotations, device, prelimin
                 pos = np.nonzero(lab_h[r, q])[0] + base
                 hit = np.nonzero(np.isin(perm, pos))[0]
                 if not len(hit):
-                    raise IndexError("index 0 is out of bounds for axis 0 with size 0 (no ground-truth-positive moment)")
+                    engine.raise_no_positive()
                 first[r, q] = hit[0]
     for r, thr in enumerate(iou_thresholds):
         if "model" in model_types:
-            recalls[("model", thr)] = {1: (ranks[r] < 1).astype(int), 10: (ranks[r] < 10).astype(int),
-                                       100: (ranks[r] < 100).astype(int), "MR": ranks[r]}
+            recalls[("model", thr)] = _rank_metrics(ranks[r], (1, 10, 100))
         if "chance" in model_types:
-            recalls[("chance", thr)] = {1: (first[r] < 1).astype(int), 10: (first[r] < 10).astype(int),
-                                        100: (first[r] < 100).astype(int), "MR": first[r]}
+            recalls[("chance", thr)] = _rank_metrics(first[r], (1, 10, 100))
     if preliminary and len(own) > preliminary and rank == 0:
         for upto in range(preliminary + 1, len(own) + 1, preliminary):   # the reference prints at li = 100, 200, ... (li + 1 queries)
             print()
             for (mt, thr), rec in recalls.items():
                 part = get_metrics({k: v[:upto] for k, v in rec.items()})
                 print(f"{mt}, IoU={thr}:\t", "".join(f"{n}: {v:.4f}\t" for n, v in part.items()))
-    model.train(was_training)
     out = {f"{mt}, IoU={thr}": get_metrics(recalls[(mt, thr)])
            for mt, thr in itertools.product(model_types, iou_thresholds) if (mt, thr) in recalls}
     if return_topk:
@@ -141,24 +172,18 @@ def validate_epoch(model, video_iterator, lang_iterator, annotations, device, si
     (``:169``), only the first ``size`` queries are scored (``:186``; ``-1`` = all, and then the 11-point threshold
     sweep with precision/recall@k, ``:137,178-179,200-206``).  A query without a positive moment raises IndexError.
     """
-    was_training = model.training
-    model.eval()
-    ops = engine.ops_for(device)
-    drained = _drain_videos(video_iterator)
     thr_range = [i / 10 for i in range(11)] if size == -1 else list(iou_thresholds)
-
-    tokens, q_videos, annot_ids = _drain_queries(lang_iterator if size <= 0 else itertools.islice(lang_iterator, size))   # :186 never fires for size <= 0
-    nq = len(tokens)
-    bert_fn = (lambda: model(torch.cat(tokens).to(device), False, device, True).contiguous()) if bert else None
-    shard, names, Q = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world, bert_fn)
-    video_index = {name: i for i, name in enumerate(names)}
-    own = np.asarray([video_index[v] for v in q_videos], np.int64)
-    times = [annotations[a]["times"] for a in annot_ids]
-    labels = engine.gt_labels(times, shard.counts_all[own], thr_range, False, shard.device, ops)   # main.py:161: >=
-    kmax = max(atk) if size == -1 else 0
-    ranks0, _, top_idx = engine.corpus_ranks(shard, Q, own, labels, ops, k=kmax, world=world)
-    ranks = ranks0.cpu().numpy() + 1                                              # :169  "+ 1"
-    model.train(was_training)
+    bert_fn = (lambda tokens: model(torch.cat(tokens).to(device), False, device, True).contiguous()) if bert else None
+    with _eval_mode(model):
+        ops, tokens, annot_ids, shard, names, Q, own = _prepare(
+            model, video_iterator, lang_iterator if size <= 0 else itertools.islice(lang_iterator, size),   # :186 never fires for size <= 0
+            device, rank, world, bert_fn, empty_ok=False)
+        nq = len(tokens)
+        times = [annotations[a]["times"] for a in annot_ids]
+        labels = engine.gt_labels(times, shard.counts_all[own], thr_range, False, shard.device, ops)   # main.py:161: >=
+        kmax = max(atk) if size == -1 else 0
+        ranks0, _, top_idx = engine.corpus_ranks(shard, Q, own, labels, ops, k=kmax, world=world)
+        ranks = ranks0.cpu().numpy() + 1                                              # :169  "+ 1"
 
     keep = [r for r, thr in enumerate(thr_range) if thr in iou_thresholds]
     tag = lambda thr: f"IoU0{round(thr * 10)}"
@@ -196,25 +221,14 @@ def evaluate_videos(model, video_iterator, lang_iterator, annotations, device, a
     ``return_topk`` = k also ``(dist, moment idx, video idx)`` [Nq, k] of the k best distinct videos per query (the
     moment is each video's best one).  Labels, IoU and annotation times play no part (``annotations`` is accepted for the
     shared signature)."""
-    was_training = model.training
-    model.eval()
-    ops = engine.ops_for(device)
-    drained = _drain_videos(video_iterator)
-    tokens, q_videos, annot_ids = _drain_queries(lang_iterator)
-    if not tokens:
-        embed_corpus(model, video_iterator, device, ops, rank, world, drained)
-        model.train(was_training)
-        out = {"video": get_metrics({k: [] for k in list(atk) + ["MR"]})}
-        return (out, (None, None, None)) if return_topk else out
-    shard, names, Q = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world)
-    video_index = {name: i for i, name in enumerate(names)}
-    own = np.asarray([video_index[v] for v in q_videos], np.int64)
-    dist, idx, vid, ranks = engine.corpus_video_topk(shard, Q, int(return_topk), own, ops, world)
-    ranks = ranks.cpu().numpy()
-    model.train(was_training)
-    rec = {k: (ranks < k).astype(int) for k in atk}
-    rec["MR"] = ranks
-    out = {"video": get_metrics(rec)}
+    with _eval_mode(model):
+        ops, _, _, shard, names, Q, own = _prepare(model, video_iterator, lang_iterator, device, rank, world)
+        if shard is None:
+            out = {"video": get_metrics(_empty_metrics(atk))}
+            return (out, (None, None, None)) if return_topk else out
+        dist, idx, vid, ranks = engine.corpus_video_topk(shard, Q, int(return_topk), own, ops, world)
+        ranks = ranks.cpu().numpy()
+    out = {"video": get_metrics(_rank_metrics(ranks, atk))}
     if return_topk:
         return out, (dist, idx, vid)
     return out
@@ -231,24 +245,15 @@ def evaluate_moments_nms(model, video_iterator, lang_iterator, annotations, devi
     ``evaluate.py:62``).  Returns ``{"model, IoU=<thr>": {"R@1", "R@10", "R@100"}}`` (``get_metrics``; no MR: a rank inside
     the diversified list is not defined here); with ``return_topk`` also ``(dist, moment idx, video idx)`` [Nq, max(atk)].
     With ``per_video`` = 0 and ``nms_iou`` >= 1 the list is the plain moment ranking and R@k equals ``evaluate``'s."""
-    was_training = model.training
-    model.eval()
-    ops = engine.ops_for(device)
-    drained = _drain_videos(video_iterator)
-    tokens, q_videos, annot_ids = _drain_queries(lang_iterator)
     K = max(atk)
-    if not tokens:
-        embed_corpus(model, video_iterator, device, ops, rank, world, drained)
-        model.train(was_training)
-        out = {f"model, IoU={thr}": get_metrics({k: [] for k in atk}) for thr in iou_thresholds}
-        return (out, (None, None, None)) if return_topk else out
-    shard, names, Q = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world)
-    video_index = {name: i for i, name in enumerate(names)}
-    own = np.asarray([video_index[v] for v in q_videos], np.int64)
-    times = [annotations[a]["times"] for a in annot_ids]
-    labels = engine.gt_labels(times, shard.counts_all[own], list(iou_thresholds), True, shard.device, ops)
-    dist, idx, vid = engine.corpus_moment_nms(shard, Q, K, per_video, nms_iou, ops, world)
-    model.train(was_training)
+    with _eval_mode(model):
+        ops, _, annot_ids, shard, names, Q, own = _prepare(model, video_iterator, lang_iterator, device, rank, world)
+        if shard is None:
+            out = {f"model, IoU={thr}": get_metrics(_empty_metrics(atk, with_mr=False)) for thr in iou_thresholds}
+            return (out, (None, None, None)) if return_topk else out
+        times = [annotations[a]["times"] for a in annot_ids]
+        labels = engine.gt_labels(times, shard.counts_all[own], list(iou_thresholds), True, shard.device, ops)
+        dist, idx, vid = engine.corpus_moment_nms(shard, Q, K, per_video, nms_iou, ops, world)
     lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
     ids, vids = idx.cpu().numpy(), vid.cpu().numpy()
     local = ids - np.asarray(shard.mom_off_all, np.int64)[own][:, None]
@@ -280,46 +285,29 @@ def evaluate_candidates(model, video_iterator, lang_iterator, annotations, devic
     [Nq, k] of the pool's k best moments (videos)."""
     if level not in ("moments", "videos"):
         raise ValueError(f"evaluate_candidates: unknown level {level!r} (moments, videos)")
-    was_training = model.training
-    model.eval()
-    ops = engine.ops_for(device)
-    drained = _drain_videos(video_iterator)
-    tokens, q_videos, annot_ids = _drain_queries(lang_iterator)
-    if not tokens:
-        empty = ({"video": get_metrics({k: [] for k in list(atk) + ["MR"]})} if level == "videos" else
-                 {f"model, IoU={thr}": get_metrics({k: [] for k in list(atk) + ["MR"]}) for thr in iou_thresholds})
-        embed_corpus(model, video_iterator, device, ops, rank, world, drained)
-        model.train(was_training)
-        return (empty, (None, None, None)) if return_topk else empty
-    shard, names, Q = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world)
-    video_index = {name: i for i, name in enumerate(names)}
-    own = np.asarray([video_index[v] for v in q_videos], np.int64)
-    pools = list(pools)
-    if len(pools) != len(own):
-        raise ValueError(f"evaluate_candidates: {len(pools)} pools for {len(own)} queries")
-    lists = engine.candidate_lists([list(p) + [int(own[q])] for q, p in enumerate(pools)], names=names)
-    K = int(return_topk)
-    if level == "videos":
-        dist, idx, vid, ranks = engine.corpus_subset_topk(shard, Q, K, lists, "videos", own_global=own, ops=ops, world=world)
-        ranks = ranks.cpu().numpy()
-        rec = {k: (ranks < k).astype(int) for k in atk}
-        rec["MR"] = ranks
-        out = {"video": get_metrics(rec)}
-    else:
-        times = [annotations[a]["times"] for a in annot_ids]
-        labels = engine.gt_labels(times, shard.counts_all[own], list(iou_thresholds), True, shard.device, ops)
-        keys = engine.best_positive_keys(shard, Q, engine.prepare_gt(shard, own, labels), ops, world)
-        if bool((keys == engine.KEY_INF).any()):
-            model.train(was_training)
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (no ground-truth-positive moment)")
-        dist, idx, vid, ranks = engine.corpus_subset_topk(shard, Q, K, lists, "moments", ops=ops, world=world, rank_keys=keys)
-        ranks = ranks.cpu().numpy()
-        out = {}
-        for r, thr in enumerate(iou_thresholds):
-            rec = {k: (ranks[r] < k).astype(int) for k in atk}
-            rec["MR"] = ranks[r]
-            out[f"model, IoU={thr}"] = get_metrics(rec)
-    model.train(was_training)
+    with _eval_mode(model):
+        ops, _, annot_ids, shard, names, Q, own = _prepare(model, video_iterator, lang_iterator, device, rank, world)
+        if shard is None:
+            empty = ({"video": get_metrics(_empty_metrics(atk))} if level == "videos" else
+                     {f"model, IoU={thr}": get_metrics(_empty_metrics(atk)) for thr in iou_thresholds})
+            return (empty, (None, None, None)) if return_topk else empty
+        pools = list(pools)
+        if len(pools) != len(own):
+            raise ValueError(f"evaluate_candidates: {len(pools)} pools for {len(own)} queries")
+        lists = engine.candidate_lists([list(p) + [int(own[q])] for q, p in enumerate(pools)], names=names)
+        K = int(return_topk)
+        if level == "videos":
+            dist, idx, vid, ranks = engine.corpus_subset_topk(shard, Q, K, lists, "videos", own_global=own, ops=ops, world=world)
+            out = {"video": get_metrics(_rank_metrics(ranks.cpu().numpy(), atk))}
+        else:
+            times = [annotations[a]["times"] for a in annot_ids]
+            labels = engine.gt_labels(times, shard.counts_all[own], list(iou_thresholds), True, shard.device, ops)
+            keys = engine.best_positive_keys(shard, Q, engine.prepare_gt(shard, own, labels), ops, world)
+            if bool((keys == engine.KEY_INF).any()):
+                engine.raise_no_positive()
+            dist, idx, vid, ranks = engine.corpus_subset_topk(shard, Q, K, lists, "moments", ops=ops, world=world, rank_keys=keys)
+            ranks = ranks.cpu().numpy()
+            out = {f"model, IoU={thr}": get_metrics(_rank_metrics(ranks[r], atk)) for r, thr in enumerate(iou_thresholds)}
     if return_topk:
         return out, (dist, idx, vid)
     return out
@@ -356,26 +344,15 @@ def evaluate_sentences(model, video_iterator, lang_iterator, annotations, device
     as ``evaluate_videos``); annotations without a span inside their video get no probe and are counted in
     ``out["sentence"]["skipped"]`` (present only when non-zero).  With ``return_topk`` = k also ``(dist, sentence idx, annotation
     rows)``: [P, k] lists of the probes and the positions in the iteration order they belong to."""
-    was_training = model.training
-    model.eval()
-    ops = engine.ops_for(device)
-    drained = _drain_videos(video_iterator)
-    tokens, q_videos, annot_ids = _drain_queries(lang_iterator)
-    if not tokens:
-        embed_corpus(model, video_iterator, device, ops, rank, world, drained)
-        model.train(was_training)
-        out = {"sentence": get_metrics({k: [] for k in list(atk) + ["MR"]})}
-        return (out, (None, None, None)) if return_topk else out
-    shard, names, S = _encode_both(model, video_iterator, drained, tokens, device, ops, rank, world)
-    video_index = {name: i for i, name in enumerate(names)}
-    own = np.asarray([video_index[v] for v in q_videos], np.int64)
-    probes, rows = sentence_probes(annotations, annot_ids, own, shard.counts_all)
-    dist, idx, ranks = engine.corpus_sentence_topk(shard, S, probes, int(return_topk), rows, ops, world)
-    ranks = ranks.cpu().numpy()
-    model.train(was_training)
-    rec = {k: (ranks < k).astype(int) for k in atk}
-    rec["MR"] = ranks
-    out = {"sentence": get_metrics(rec)}
+    with _eval_mode(model):
+        ops, _, annot_ids, shard, names, S, own = _prepare(model, video_iterator, lang_iterator, device, rank, world)
+        if shard is None:
+            out = {"sentence": get_metrics(_empty_metrics(atk))}
+            return (out, (None, None, None)) if return_topk else out
+        probes, rows = sentence_probes(annotations, annot_ids, own, shard.counts_all)
+        dist, idx, ranks = engine.corpus_sentence_topk(shard, S, probes, int(return_topk), rows, ops, world)
+        ranks = ranks.cpu().numpy()
+    out = {"sentence": get_metrics(_rank_metrics(ranks, atk))}
     if len(rows) < len(annot_ids):
         out["sentence"]["skipped"] = len(annot_ids) - len(rows)
     if return_topk:
