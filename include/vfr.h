@@ -293,6 +293,51 @@ int vfr_score_sentences_f32(const float *S, int64_t Ns, const float *V, const in
                             int64_t sent_base, int k, float *out_dist, int64_t *out_idx, int num_rank, const float *rank_dist,
                             const int64_t *rank_idx, int64_t *count_lt, int *bad, void *workspace, size_t workspace_bytes,
                             vfr_stream_t stream);
+/* ---- paragraph-to-video retrieval: which VIDEO does a group of sentences describe (the paragraph-to-video protocol of datasets
+ * with several descriptions per video).  Q [Nq, D] = the sentences; a paragraph is a run of consecutive rows: grp_off [Ng+1]
+ * (device int64, non-decreasing from 0 to Nq); max_len (host) = the longest run, <= 64.
+ *   b(j, v)     = the distance of video v's best key for sentence j, exactly vfr_score_video_topk_f32's (the smallest (distance,
+ *           global moment id) key over the whole triangle, canonical chain); m(j, v) = that key's moment id.
+ *   score(g, v) = (b(j0, v) + b(j0+1, v) + .. + b(j0+L-1, v)) / (float)L: one fp32 left-to-right chain in sentence order starting
+ *           from b(j0, v), then one correctly rounded fp32 division; nothing is contracted into an fma.
+ *   key = (fp32 bits of score << 32) | (vid_base + v), order (score, global video index) ascending.  A video without clips is never
+ *           ranked; an empty group gives padding and adds nothing.  With every group of length 1 out_dist equals
+ *           vfr_score_video_topk_f32's out_dist bit for bit and the videos are those of its out_idx, in the same order.
+ * vfr_score_paragraphs_f32:
+ *   k > 0 : out_dist / out_idx [Ng,k] = the k smallest keys over the bank's videos as (score, global video index), padded with
+ *           (+inf, -1).  k = 0 with counts only is allowed.
+ *   own_dist / own_idx / count_lt [Ng] (nullable, together): count_lt[g] (int64) += number of this bank's videos whose key sorts
+ *           strictly before (own_dist[g], own_idx[g]).  ADDED, so shards chain; the lists merge with vfr_topk_merge_f32.
+ *   dtype VFR_SCORE_EXACT or VFR_MFMA_F32 (| VFR_MFMA_BANK_READY), as vfr_score_video_topk_f32: the fast path (D = 100, <= 21 clips,
+ *           banks of at least score_mfma_min videos) runs the score's own chain on rigorous per-(sentence, video) bounds, keeps the
+ *           videos the bounds cannot exclude or count, and gives those the exact chain.  BIT-IDENTICAL outputs.  The workspace front
+ *           is vfr_score_video_topk_f32's, so BANK_READY and the device hash work alike.
+ *   bad (nullable, device int): set to 1 when grp_off is not a non-decreasing run from 0 to Nq or a group is longer than max_len
+ *           (results for such input are unspecified; nothing is read or written out of bounds).
+ * vfr_score_paragraph_pairs_f32: pairs int32 [Np,2] = (group, GLOBAL video).  out_score [Np] = score(group, video);
+ *   out_moments int64 [Np,max_len] (nullable) = m(j, video) per sentence of the group, -1 past the group's length.  A pair whose
+ *   video lies outside [vid_base, vid_base + Nv) is left untouched: pre-fill +inf / -1 and reduce MIN / MAX over shards.  A pair on a
+ *   video without clips or an empty group gets (+inf, -1); a group index outside [0, Ng) sets bad and is left untouched.  Serves the
+ *   own video's rank key and the grounding of returned videos (where in video v each sentence lands).
+ * Limits: k <= 448, max_clips <= 64, max_len <= 64, Ng * k < 2^31, vid_base + Nv < 2^32, id_base + total moments < 2^32.  Bad host
+ * arguments: VFR_EINVAL before anything is enqueued.  The kernels keep one sentence row and the lanes' clip distances in 64 KB of
+ * LDS: 4 * (round_up(D, 4) + 64 * max(max_clips, 1)) bytes for vfr_score_paragraphs_f32 (D <= 12288 at max_clips = 64, more for
+ * shorter videos) and 4 * (round_up(D, 4) + 64) bytes for the pairs call must fit; VFR_EUNSUPPORTED otherwise, before anything is
+ * enqueued.  vfr_score_paragraphs_workspace_bytes: O((Nq + Ng) Nv) (0 for a bad argument).
+ * vfr_score_paragraphs_stats (measurement hook, SYNCHRONISES the stream): what the last VFR_MFMA_F32 fast-path call on `workspace`
+ * (same Nq, Ng, Nv, total_clips) re-scored exactly: stats_host [Ng, 2] = {videos given the exact chain, of them rank-undecided}. */
+size_t vfr_score_paragraphs_workspace_bytes(int64_t Nq, int64_t Ng, int Nv, int total_clips, int k);
+int vfr_score_paragraphs_f32(const float *Q, int64_t Nq, const int64_t *grp_off, int64_t Ng, int max_len, const float *V,
+                             const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv, int total_clips, int min_clips,
+                             int max_clips, int D, float eps, int64_t vid_base, int k, float *out_dist, int64_t *out_idx,
+                             const float *own_dist, const int64_t *own_idx, int64_t *count_lt, int dtype, int *bad,
+                             void *workspace, size_t workspace_bytes, vfr_stream_t stream);
+int vfr_score_paragraph_pairs_f32(const float *Q, int64_t Nq, const int64_t *grp_off, int64_t Ng, int max_len, const float *V,
+                                  const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv, int total_clips, int min_clips,
+                                  int max_clips, int D, float eps, int64_t id_base, int64_t vid_base, const int32_t *pairs, int64_t Np,
+                                  float *out_score, int64_t *out_moments, int *bad, vfr_stream_t stream);
+int vfr_score_paragraphs_stats(const void *workspace, int64_t Nq, int64_t Ng, int Nv, int total_clips, int64_t *stats_host,
+                               vfr_stream_t stream);
 /* Device self-check of the arithmetic model the pre-filter's margins and the MFMA GEMMs' bit-exactness assume: a
  * v_mfma_f32_16x16x4_f32 = four fp32 fmas, k ascending, on its accumulator (denormals kept).  A, B [16, K] device rows
  * (K % 4 == 0; make them adversarial: wide exponent range, cancellation, denormals): C = A B^T by the matrix pipe against an

@@ -65,6 +65,12 @@ SIGNATURES = {
     "vfr_score_sentences_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "vfr_score_sentences_f32": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32,
                                        _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vfr_score_paragraphs_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "vfr_score_paragraphs_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _vp, _vp,
+                                        _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "vfr_score_paragraph_pairs_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i64,
+                                             _vp, _i64, _vp, _vp, _vp, _vp]),
+    "vfr_score_paragraphs_stats": (_i32, [_vp, _i64, _i64, _i32, _i32, ctypes.POINTER(ctypes.c_int64), _vp]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "vfr_topk_pack_keys": (_i32, [_vp, _vp, _i64, _vp, _vp]),
@@ -656,6 +662,86 @@ def score_sentences(S: torch.Tensor, bank: VideoBank, probes: torch.Tensor, k: i
         if R:
             count_lt.index_add_(1, order, cl)
     return od, oi, count_lt
+
+
+def _group_args(Q: torch.Tensor, bank: VideoBank, grp_off: torch.Tensor, max_len: int, eps: float, who: str):
+    """The leading arguments the paragraph entry points share: sentences, groups, the bank's CSR, eps -> (arguments, Ng)."""
+    grp_off = _dev(grp_off, torch.int64, "grp_off")
+    if grp_off.dim() != 1 or grp_off.numel() < 1:
+        raise RuntimeError(f"{who}: grp_off must be int64 [Ng + 1]")
+    if Q.dim() != 2 or Q.shape[1] != bank.dim:
+        raise RuntimeError(f"{who}: Q must be [Nq, {bank.dim}], got {tuple(Q.shape)}")
+    Ng = int(grp_off.numel()) - 1
+    return (Q.data_ptr(), Q.shape[0], grp_off.data_ptr(), Ng, int(max_len), bank.emb.data_ptr(), bank.clip_off.data_ptr(),
+            bank.mom_off.data_ptr(), bank.num_videos, bank.total_clips, bank.min_clips, bank.max_clips, bank.dim, eps), Ng, grp_off
+
+
+def score_paragraphs(Q: torch.Tensor, bank: VideoBank, grp_off: torch.Tensor, max_len: int, k: int, vid_base: int = 0, own_dist=None,
+                     own_idx=None, count=None, mode: str | None = None, workspace: torch.Tensor | None = None,
+                     bad: torch.Tensor | None = None, eps: float = 1e-6):
+    """Paragraph-to-video retrieval (include/vfr.h vfr_score_paragraphs_f32): ``Q`` [Nq, D] sentences, a paragraph = the run of rows
+    ``grp_off[g] .. grp_off[g+1]`` (device int64 [Ng+1]; ``max_len`` = the longest run, <= 64).  The score of (paragraph, video) is
+    the fp32 mean, in sentence order, of the video's best distance for each sentence; keys are (score, ``vid_base`` + video).
+    Returns the k best videos per paragraph (score [Ng,k] | None, global video index [Ng,k] int64 | None; padded with (+inf, -1)) and,
+    with ``own_dist`` / ``own_idx`` [Ng] (``score_paragraph_pairs`` of the own video), ``count`` [Ng] int64 += the number of this
+    bank's videos whose key sorts before it (allocated zeroed when None).  ``mode``: "mfma" or "exact" (same bits); None =
+    DEFAULT_SCORE_MODE.  ``bad`` (device int32 [1], nullable) is set to 1 for a malformed ``grp_off``."""
+    dtype, Q = _video_mode(mode, Q, "score_paragraphs")
+    args, Ng, grp_off = _group_args(Q, bank, grp_off, max_len, eps, "score_paragraphs")
+    od, oi = _out_lists(Ng, k, Q.device)
+    own_dist, own_idx, cnt, R = _rank_keys(own_dist, own_idx, count, Ng, Q.device, ("own_dist", "own_idx", "count"))
+    if R:                                    # ONE key per paragraph, and the public count is [Ng]
+        own_dist, own_idx = own_dist.reshape(Ng), own_idx.reshape(Ng)
+        if count is None:
+            cnt = cnt.reshape(Ng)
+    if bad is not None:
+        bad = _dev(bad, torch.int32, "bad")
+    nbytes = lib().vfr_score_paragraphs_workspace_bytes(Q.shape[0], Ng, bank.num_videos, bank.total_clips, k)
+    workspace = _workspace(workspace, nbytes, Q.device)
+    token, ready = _video_bank_ready(workspace, bank, dtype, eps)       # the workspace front is score_video_topk's
+    _check(lib().vfr_score_paragraphs_f32(*args, int(vid_base), k, _ptr(od), _ptr(oi), _ptr(own_dist), _ptr(own_idx), _ptr(cnt),
+                                          dtype | (MFMA_BANK_READY if ready else 0), _ptr(bad), workspace.data_ptr(), nbytes, _stream()),
+           "vfr_score_paragraphs_f32")
+    _video_bank_claim(workspace, token, bank, dtype, ran=Ng > 0 and Q.shape[0] > 0 and max_len > 0 and (k > 0 or R > 0))
+    return od, oi, cnt
+
+
+def score_paragraph_pairs(Q: torch.Tensor, bank: VideoBank, grp_off: torch.Tensor, max_len: int, pairs: torch.Tensor, vid_base: int = 0,
+                          out_score: torch.Tensor | None = None, out_moments: torch.Tensor | None = None, moments: bool = True,
+                          bad: torch.Tensor | None = None, eps: float = 1e-6):
+    """Named (paragraph, video) pairs (include/vfr.h vfr_score_paragraph_pairs_f32): ``pairs`` int32 [Np, 2] = (group, GLOBAL video
+    index).  Returns (score [Np], moments int64 [Np, max_len] | None): the paragraph score of each pair and, per sentence of the
+    group, the global id of the video's best moment (-1 past the group's length).  Pairs of videos outside this bank (``vid_base``
+    .. + its videos) are left untouched: the outputs are allocated pre-filled with +inf / -1 (or pass ``out_score`` /
+    ``out_moments`` of another shard's call to chain).  ``moments=False`` skips the grounding."""
+    Q = _dev(Q, torch.float32, "Q")
+    pairs = _dev(pairs, torch.int32, "pairs")
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise RuntimeError(f"score_paragraph_pairs: pairs must be [Np, 2] (group, video), got {tuple(pairs.shape)}")
+    args, Ng, grp_off = _group_args(Q, bank, grp_off, max_len, eps, "score_paragraph_pairs")
+    Np = int(pairs.shape[0])
+    if out_score is None:
+        out_score = torch.full((Np,), float("inf"), dtype=torch.float32, device=Q.device)
+    out_score = _dev(out_score, torch.float32, "out_score")
+    if moments and out_moments is None:
+        out_moments = torch.full((Np, int(max_len)), -1, dtype=torch.int64, device=Q.device)
+    if out_moments is not None:
+        out_moments = _dev(out_moments, torch.int64, "out_moments")
+    if bad is not None:
+        bad = _dev(bad, torch.int32, "bad")
+    _check(lib().vfr_score_paragraph_pairs_f32(*args, bank.id_base, int(vid_base), _ptr(pairs) if Np else 0, Np, _ptr(out_score) if Np else 0,
+                                               _ptr(out_moments) if Np and max_len else 0, _ptr(bad), _stream()),
+           "vfr_score_paragraph_pairs_f32")
+    return out_score, out_moments
+
+
+def score_paragraphs_stats(workspace: torch.Tensor, Nq: int, Ng: int, bank: VideoBank) -> np.ndarray:
+    """[Ng, 2] int64 of the last ``mode="mfma"`` fast-path ``score_paragraphs`` call on ``workspace``: videos given the exact chain
+    per paragraph, and how many of them were undecided rank counts (synchronises)."""
+    out = np.zeros((Ng, 2), np.int64)
+    _check(lib().vfr_score_paragraphs_stats(workspace.data_ptr(), Nq, Ng, bank.num_videos, bank.total_clips,
+                                            out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _stream()), "vfr_score_paragraphs_stats")
+    return out
 
 
 def nms_inter_table(nms_iou: float, max_len: int = 64) -> np.ndarray:

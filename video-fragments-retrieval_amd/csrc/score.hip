@@ -2551,3 +2551,6 @@ extern "C" int vfr_mfma_selfcheck(const float *A, const float *B, int K, int rev
 
 // diversified moment retrieval: per-video cap and temporal NMS over the video top-k above
 #include "moment_nms.h"
+
+// paragraph-to-video retrieval: groups of sentences against the video bounds / exact triangles above
+#include "paragraphs.h"

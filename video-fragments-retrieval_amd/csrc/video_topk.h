@@ -410,6 +410,35 @@ static VtkWs carve_vtk(void *base, int64_t Nq, int Nv, int total_clips)
     return w;
 }
 
+// the fast path's pre-pass: exactly the pre-filter's bank-side sequence (hash guard, mean, centred rows, a_c, largest norm; no
+// bf16 copy), then the centred query rows and their meta.  Shared by every entry point that builds on vtk_bounds_kernel.
+static int vtk_prepass(MfmaWs &mw, float *qc, float4 *qmeta, const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets,
+                       int Nv, int total_clips, int D, float eps, bool bank_ready, hipStream_t st)
+{
+    ProfScope prof(SITE_SCORE_PREP, st);
+    {
+        const FillJob jobs[1] = {{mw.zero_base, nullptr, (size_t)(reinterpret_cast<char *>(mw.stale) - static_cast<char *>(mw.zero_base)) + 4, 0u}};
+        if (int rc = fill_regions(jobs, 1, st)) return rc;
+    }
+    BankSig now{};
+    now.total_clips = total_clips; now.Nv = Nv; now.D = D; now.eps_bits = __builtin_bit_cast(unsigned, eps); now.has_bf16 = 0;
+    const int64_t nwords = (int64_t)total_clips * D;
+    int hb = (int)cdiv(nwords, 256 * 4 * 8);
+    hb = hb < 1 ? 1 : (hb > 2048 ? 2048 : hb);
+    hipLaunchKernelGGL(mfma_bank_hash_kernel, dim3((unsigned)hb), dim3(256), 0, st, reinterpret_cast<const unsigned *>(V), nwords,
+                       reinterpret_cast<const unsigned *>(clip_offsets), (int64_t)Nv + 1, mw.hash_now);
+    hipLaunchKernelGGL(mfma_bank_check_kernel, dim3(1), dim3(1), 0, st, mw.hash_now, now, bank_ready ? 1 : 0, mw.sig, mw.stale, mw.rv);
+    hipLaunchKernelGGL(mfma_mean_partial_kernel, dim3((unsigned)mw.mean_blocks), dim3(1024), 0, st, V, total_clips, D, mw.mean_rows,
+                       mw.mean_partial, mw.stale);
+    hipLaunchKernelGGL(mfma_mean_final_kernel, dim3(1), dim3(1024), 0, st, mw.mean_partial, mw.mean_blocks, D, total_clips, mw.mu, mw.stale);
+    hipLaunchKernelGGL(mfma_prep_v_kernel, dim3((unsigned)cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps,
+                       mw.mu, mw.vc, mw.va, mw.rv, (unsigned short *)nullptr, mw.stale);
+    hipLaunchKernelGGL(mfma_prep_q_kernel, dim3((unsigned)cdiv(Nq, 16)), dim3(256), 0, st, Q, Nq, D, eps, mw.mu, qc, mw.rv,
+                       0, (const float *)nullptr, qmeta);
+    VFR_CHECK_LAUNCH("video top-k pre-pass");
+    return VFR_OK;
+}
+
 }  // namespace vfr
 
 extern "C" {
@@ -468,31 +497,8 @@ int vfr_score_video_topk_f32(const float *Q, int64_t Nq, const float *V, const i
                       ((((uintptr_t)Q) | ((uintptr_t)V)) & 15) == 0;
     const unsigned *list = nullptr;
     const int *list_len = nullptr;
-    if (fast) {
-        vfr::ProfScope prof(vfr::SITE_SCORE_PREP, st);
-        {
-            const vfr::FillJob jobs[1] = {{w.mw.zero_base, nullptr, (size_t)(reinterpret_cast<char *>(w.mw.stale) - static_cast<char *>(w.mw.zero_base)) + 4, 0u}};
-            if (int rc = vfr::fill_regions(jobs, 1, st)) return rc;
-        }
-        // bank side: exactly the pre-filter's sequence (hash guard, mean, centred rows, a_c, largest norm); no bf16 copy
-        vfr::BankSig now{};
-        now.total_clips = total_clips; now.Nv = Nv; now.D = D; now.eps_bits = __builtin_bit_cast(unsigned, eps); now.has_bf16 = 0;
-        const int64_t nwords = (int64_t)total_clips * D;
-        int hb = (int)vfr::cdiv(nwords, 256 * 4 * 8);
-        hb = hb < 1 ? 1 : (hb > 2048 ? 2048 : hb);
-        vfr::MfmaWs &mw = w.mw;
-        hipLaunchKernelGGL(vfr::mfma_bank_hash_kernel, dim3((unsigned)hb), dim3(256), 0, st, reinterpret_cast<const unsigned *>(V), nwords,
-                           reinterpret_cast<const unsigned *>(clip_offsets), (int64_t)Nv + 1, mw.hash_now);
-        hipLaunchKernelGGL(vfr::mfma_bank_check_kernel, dim3(1), dim3(1), 0, st, mw.hash_now, now, bank_ready ? 1 : 0, mw.sig, mw.stale, mw.rv);
-        hipLaunchKernelGGL(vfr::mfma_mean_partial_kernel, dim3((unsigned)mw.mean_blocks), dim3(1024), 0, st, V, total_clips, D, mw.mean_rows,
-                           mw.mean_partial, mw.stale);
-        hipLaunchKernelGGL(vfr::mfma_mean_final_kernel, dim3(1), dim3(1024), 0, st, mw.mean_partial, mw.mean_blocks, D, total_clips, mw.mu, mw.stale);
-        hipLaunchKernelGGL(vfr::mfma_prep_v_kernel, dim3((unsigned)vfr::cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps,
-                           mw.mu, mw.vc, mw.va, mw.rv, (unsigned short *)nullptr, mw.stale);
-        hipLaunchKernelGGL(vfr::mfma_prep_q_kernel, dim3((unsigned)vfr::cdiv(Nq, 16)), dim3(256), 0, st, Q, Nq, D, eps, mw.mu, w.qc, mw.rv,
-                           0, (const float *)nullptr, w.qmeta);
-        VFR_CHECK_LAUNCH("video top-k pre-pass");
-    }
+    if (fast)
+        if (int rc = vfr::vtk_prepass(w.mw, w.qc, w.qmeta, Q, Nq, V, clip_offsets, Nv, total_clips, D, eps, bank_ready, st)) return rc;
     if (fast) {
         vfr::ProfScope prof(vfr::SITE_SCORE_FUSED, st);
         hipLaunchKernelGGL(vfr::vtk_bounds_kernel, dim3((unsigned)vfr::cdiv(Nv, vfr::VTK_VIDEOS), (unsigned)vfr::cdiv(Nq, 64)), dim3(64), 0, st,

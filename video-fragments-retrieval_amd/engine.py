@@ -69,6 +69,15 @@ class HipOps:
         return self.v.score_sentences(S, bank, probes, k, vid_base, sent_base, rank_dist, rank_idx, count_lt=count_lt, bad=bad,
                                       workspace=workspace)
 
+    def score_paragraphs(self, Q, bank, grp_off, max_len, k, vid_base=0, own_dist=None, own_idx=None, count=None, workspace=None,
+                         bad=None):
+        return self.v.score_paragraphs(Q, bank, grp_off, max_len, k, vid_base, own_dist, own_idx, count=count, workspace=workspace,
+                                       bad=bad, mode=self._video_mode())
+
+    def score_paragraph_pairs(self, Q, bank, grp_off, max_len, pairs, vid_base=0, out_score=None, out_moments=None, moments=True,
+                              bad=None):
+        return self.v.score_paragraph_pairs(Q, bank, grp_off, max_len, pairs, vid_base, out_score, out_moments, moments, bad=bad)
+
     def slice_bank(self, bank, counts, v0, v1):
         return self.v.slice_bank(bank, counts, v0, v1)
 
@@ -845,6 +854,96 @@ def corpus_sentence_topk(shard: CorpusShard, S, probes, k, own_sentence=None, op
     return od, oi, (cnt[0] if cnt is not None else None)
 
 
+PARAGRAPH_MAX_LEN = 64                    # include/vfr.h: sentences per paragraph
+
+
+@dataclass
+class ParagraphGroups:
+    """Paragraphs as runs of consecutive sentence rows (``paragraph_groups``): ``off`` [Ng+1] int64 on the host, non-decreasing from
+    0 to the number of sentences; ``max_len`` = the longest run.  ``on(device)`` uploads ``off`` once."""
+    off: np.ndarray
+    max_len: int
+    _dev: dict = None
+
+    @property
+    def num_groups(self):
+        return len(self.off) - 1
+
+    @property
+    def num_sentences(self):
+        return int(self.off[-1])
+
+    def on(self, device):
+        device = torch.device(device)
+        if self._dev is None:
+            self._dev = {}
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.off).to(device)
+        return self._dev[key]
+
+
+def paragraph_groups(lengths=None, labels=None, device=None) -> ParagraphGroups:
+    """Paragraph runs from ``lengths`` (sentences per paragraph, 0 allowed: an empty paragraph) or from ``labels`` (one per
+    sentence row: every maximal run of equal consecutive labels is a paragraph -- sort the rows by label first, stably, to get one
+    paragraph per label).  A paragraph longer than 64 sentences raises ValueError.  ``device``: upload the offsets there as well."""
+    if (lengths is None) == (labels is None):
+        raise ValueError("paragraph_groups: give lengths or labels")
+    if lengths is None:
+        lab = list(labels)
+        starts = [i for i in range(len(lab)) if i == 0 or lab[i] != lab[i - 1]]
+        lengths = np.diff(np.asarray(starts + [len(lab)], np.int64))
+    lens = np.asarray(lengths, np.int64).reshape(-1)
+    if len(lens) and lens.min() < 0:
+        raise ValueError("paragraph_groups: negative length")
+    longest = int(lens.max()) if len(lens) else 0
+    if longest > PARAGRAPH_MAX_LEN:
+        raise ValueError(f"paragraph_groups: a paragraph of {longest} sentences (at most {PARAGRAPH_MAX_LEN})")
+    out = ParagraphGroups(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), longest)
+    if device is not None:
+        out.on(device)
+    return out
+
+
+def corpus_paragraph_topk(shard: CorpusShard, Q, groups: ParagraphGroups, k, own_global=None, ground=False, ops=None, world=1,
+                          workspace=None):
+    """Paragraph-to-video retrieval over the corpus: per paragraph (``paragraph_groups`` over the rows of ``Q``) the k videos with
+    the smallest score = fp32 mean, in sentence order, of the video's best moment distance for each sentence, in (score, global
+    video index) order.  With ``own_global`` [Ng] (each paragraph's own global video index) also its 0-based rank = the number of
+    videos whose key sorts strictly before the own video's key; the own key comes from one pairs launch on the rank that holds the
+    video, MIN-reduced.  ``ground``: also where each sentence lands in each returned video (global id of that video's best moment
+    for the sentence; -1 past the paragraph's length and for padding) from one pairs launch on the merged result, MAX-reduced.  A
+    video never spans shards, so the lists merge with the key merge and the counts add.
+    Returns (score [Ng,k], video index [Ng,k] int64 (-1 = padding), ranks [Ng] int64 | None, moments [Ng,k,max_len] int64 | None);
+    score / video are None for k = 0."""
+    ops = ops or HipOps()
+    if groups.num_sentences != Q.shape[0]:
+        raise ValueError(f"corpus_paragraph_topk: the groups cover {groups.num_sentences} sentences, Q has {Q.shape[0]}")
+    Ng, dev = groups.num_groups, shard.device
+    off_t = groups.on(dev)
+    dist = _group(world)
+    own_d = own_i = None
+    if own_global is not None:
+        own = np.asarray(own_global.cpu() if isinstance(own_global, torch.Tensor) else own_global, np.int64).reshape(-1)
+        if len(own) != Ng:
+            raise ValueError(f"corpus_paragraph_topk: {len(own)} own videos for {Ng} paragraphs")
+        pairs = torch.from_numpy(np.stack([np.arange(Ng, dtype=np.int64), own], axis=1).astype(np.int32)).to(dev)
+        own_d, _ = ops.score_paragraph_pairs(Q, shard.bank, off_t, groups.max_len, pairs, shard.lo, moments=False)
+        if dist is not None:
+            dist.all_reduce(own_d, op=dist.ReduceOp.MIN)
+        own_i = torch.from_numpy(own).to(dev)
+    od, oi, cnt = _exchange(*ops.score_paragraphs(Q, shard.bank, off_t, groups.max_len, k, shard.lo, own_d, own_i, workspace=workspace),
+                            k, ops, world)
+    moments = None
+    if ground and k > 0:
+        pairs = torch.stack([torch.arange(Ng, device=oi.device)[:, None].expand(Ng, k), oi], dim=2).reshape(Ng * k, 2).to(torch.int32)
+        _, moments = ops.score_paragraph_pairs(Q, shard.bank, off_t, groups.max_len, pairs.contiguous(), shard.lo)
+        if dist is not None:
+            dist.all_reduce(moments, op=dist.ReduceOp.MAX)
+        moments = moments.reshape(Ng, k, groups.max_len)
+    return od, oi, cnt, moments
+
+
 def video_results(ids, dist, names, counts_all, mom_off_all):
     """Search results as rows: per query a list of (video name, start_t, end_t, distance) for the global moment ids ``ids``
     [Nq, k] (``corpus_video_topk`` / ``corpus_topk``); start_t / end_t are the inclusive clip span of the moment
@@ -1006,13 +1105,48 @@ class TorchCpuOps:
             cols.append(acc / float(e - s + 1))
         return torch.stack(cols, dim=1) if cols else dist_v.new_zeros((dist_v.shape[0], 0))
 
+    @staticmethod
+    def _fma32(t, acc):
+        """fp32 fma(t, t, acc) for acc >= 0, correctly rounded.  t * t is exact in float64 and s = acc + t * t is rounded once there;
+        rounding s again to fp32 can only differ from rounding the exact sum when s is inexact AND sits on an fp32 midpoint (or the
+        result is subnormal).  Those few elements are redone with s rounded to odd (the two-sum's error term gives the sticky bit;
+        53 >= 2 * 24 + 2 bits make the final rounding exact)."""
+        a = acc.astype(np.float64)
+        p = t.astype(np.float64)
+        p *= p
+        s = a + p
+        out = s.astype(np.float32)
+        i = np.flatnonzero(((s.view(np.int64) & 0x1FFFFFFF) == 0x10000000) | (s < 2.0 ** -125))
+        if len(i):
+            a, p, s = a.ravel()[i], p.ravel()[i], s.ravel()[i]
+            bb = s - a
+            err = (a - (s - bb)) + (p - bb)
+            bits = s.view(np.int64)
+            odd = np.where(err > 0, bits | 1, (bits - 1) | 1)             # exact sum above / below s (s > 0 whenever err != 0)
+            out.ravel()[i] = np.where(err == 0, bits, odd).view(np.float64).astype(np.float32)
+        return out
+
+    @classmethod
+    def _clip_dist(cls, Q, V, eps=1e-6):
+        """[Nq, C] clip distances ||(v - q) + eps||_2 with the kernels' own chain -- k-ascending fp32 fma of ((v - q) + eps)^2 and
+        an IEEE sqrt -- so every score of this provider carries the HIP path's bits (a vectorised sum orders the additions
+        differently).  The ONE distance of the provider: lists, own keys and rank counts all compare keys built on it."""
+        q, v = Q.float().numpy(), V.float().numpy()
+        e32 = np.float32(eps)
+        out = np.empty((q.shape[0], v.shape[0]), np.float32)
+        step = max(1, 32768 // max(1, q.shape[0]))                        # clips per block: the temporaries stay in cache
+        for c0 in range(0, v.shape[0], step):
+            vb = v[c0:c0 + step]
+            acc = np.zeros((q.shape[0], vb.shape[0]), np.float32)
+            for kk in range(q.shape[1]):
+                acc = cls._fma32((vb[None, :, kk] - q[:, None, kk]) + e32, acc)
+            out[:, c0:c0 + step] = np.sqrt(acc)
+        return torch.from_numpy(out)
+
     def _dense(self, Q, bank, eps=1e-6):
-        out = []
+        d = self._clip_dist(Q, bank.emb, eps)
         off = bank.clip_off.tolist()
-        for v in range(len(off) - 1):
-            V = bank.emb[off[v]:off[v + 1]]
-            d = ((V[None, :, :] - Q[:, None, :]) + eps).pow(2).sum(-1).sqrt()
-            out.append(self._video_scores(d))
+        out = [self._video_scores(d[:, off[v]:off[v + 1]]) for v in range(len(off) - 1)]
         return torch.cat(out, dim=1) if out else Q.new_zeros((Q.shape[0], 0))
 
     def score_own(self, Q, bank, own_local, eps=1e-6):
@@ -1022,7 +1156,7 @@ class TorchCpuOps:
         off = bank.clip_off.tolist()
         for q, v in enumerate(own_local.tolist()):
             V = bank.emb[off[v]:off[v + 1]]
-            d = ((V - Q[q][None, :]) + eps).pow(2).sum(-1).sqrt()[None, :]
+            d = self._clip_dist(Q[q:q + 1], V, eps)
             sc = self._video_scores(d)[0]
             out[q, :sc.numel()] = sc
         return out
@@ -1162,13 +1296,95 @@ class TorchCpuOps:
             if wrong or not owned:
                 continue
             V = bank.emb[off[lv] + s0:off[lv] + e0 + 1]
-            d = ((V[None, :, :] - S[:, None, :]) + eps).pow(2).sum(-1).sqrt()
+            d = self._clip_dist(S, V, eps)
             acc = d[:, 0]
             for c in range(1, d.shape[1]):
                 acc = acc + d[:, c]
             out[m] = _pack_key(acc / float(e0 - s0 + 1), ids)
         kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nm), rank_idx.reshape(-1, Nm))
         return self._topk_lists(out, k) + (self._counts_below(out, kstar, count_lt),)
+
+    def _video_best_keys(self, Q, bank):
+        """[Nq, Nv] packed (distance, global moment id) best key of every video for every row of ``Q`` (KEY_INF: no clips)."""
+        keys = self._dense_keys(Q, bank)
+        mo = csr_offsets(bank.counts)[1]
+        cols = [keys[:, int(a):int(b)].min(dim=1).values if b > a else torch.full((Q.shape[0],), KEY_INF, dtype=torch.int64)
+                for a, b in zip(mo[:-1], mo[1:])]
+        return torch.stack(cols, dim=1) if cols else torch.zeros((Q.shape[0], 0), dtype=torch.int64)
+
+    @staticmethod
+    def _group_runs(grp_off, Nq, max_len, bad):
+        """The runs of ``grp_off`` as (j0, L) clamped like the kernels clamp them; ``bad`` is set for a malformed ``grp_off``."""
+        off = [int(x) for x in torch.as_tensor(grp_off).tolist()]
+        runs, wrong = [], off[0] != 0 or off[-1] != Nq
+        for a, b in zip(off[:-1], off[1:]):
+            wrong = wrong or b < a or b - a > max_len
+            a = min(max(a, 0), Nq)
+            b = min(max(b, a), Nq, a + max_len)
+            runs.append((a, b - a))
+        if wrong and bad is not None:
+            bad.fill_(1)
+        return runs
+
+    @staticmethod
+    def _paragraph_score(dist_rows):
+        """[L, n] best distances -> [n] paragraph scores: the fp32 chain in sentence order, then one division."""
+        acc = dist_rows[0]
+        for t in range(1, dist_rows.shape[0]):
+            acc = acc + dist_rows[t]
+        return acc / float(dist_rows.shape[0])
+
+    def score_paragraphs(self, Q, bank, grp_off, max_len, k, vid_base=0, own_dist=None, own_idx=None, count=None, workspace=None,
+                         bad=None):
+        """Paragraph-to-video retrieval from the dense scores (same semantics and bits as ``_vfr.score_paragraphs``): per
+        (sentence, video) the smallest (score, id) key, per paragraph the fp32 chain of their distances in sentence order and one
+        division, keys (score, vid_base + video); the k smallest and the number of videos below the own key."""
+        Q = Q.float()
+        best = _unpack_key(self._video_best_keys(Q, bank))[0]
+        live = torch.tensor([n > 0 for n in bank.counts], dtype=torch.bool)
+        vids = vid_base + torch.arange(len(bank.counts))
+        runs = self._group_runs(grp_off, Q.shape[0], max_len, bad)
+        keys = torch.full((len(runs), len(bank.counts)), KEY_INF, dtype=torch.int64)
+        for g, (j0, L) in enumerate(runs):
+            if L > 0 and len(vids):
+                kk = _pack_key(self._paragraph_score(best[j0:j0 + L]), vids)
+                keys[g] = torch.where(live, kk, torch.full_like(kk, KEY_INF))
+        if own_dist is not None:
+            Ng = len(runs)
+            real = torch.where(keys == KEY_INF, torch.full_like(keys, torch.iinfo(torch.int64).max), keys)    # never counted
+            count = self._counts_below(real, _pack_key(own_dist.reshape(1, Ng), own_idx.reshape(1, Ng)), count)[0]
+        return self._topk_lists(keys, k) + (count,)
+
+    def score_paragraph_pairs(self, Q, bank, grp_off, max_len, pairs, vid_base=0, out_score=None, out_moments=None, moments=True,
+                              bad=None):
+        """Named (paragraph, global video) pairs (same semantics as ``_vfr.score_paragraph_pairs``): the paragraph score and, per
+        sentence, the global id of the video's best moment; pairs of other shards are left untouched (+inf / -1 pre-filled)."""
+        Q = Q.float()
+        rows = [[int(x) for x in r] for r in torch.as_tensor(pairs).tolist()]
+        Np, Nv = len(rows), len(bank.counts)
+        if out_score is None:
+            out_score = torch.full((Np,), float("inf"))
+        if moments and out_moments is None:
+            out_moments = torch.full((Np, int(max_len)), -1, dtype=torch.int64)
+        runs = self._group_runs(grp_off, Q.shape[0], max_len, bad)
+        bk = self._video_best_keys(Q, bank)
+        bd, bi = _unpack_key(bk)
+        for p, (g, gv) in enumerate(rows):
+            lv = gv - vid_base
+            if g < 0 or g >= len(runs):
+                if bad is not None:
+                    bad.fill_(1)
+                continue
+            if lv < 0 or lv >= Nv:
+                continue
+            j0, L = runs[g]
+            ranked = L > 0 and bank.counts[lv] > 0
+            out_score[p] = self._paragraph_score(bd[j0:j0 + L, lv:lv + 1])[0] if ranked else float("inf")
+            if out_moments is not None:
+                out_moments[p] = -1
+                if ranked:
+                    out_moments[p, :L] = bi[j0:j0 + L, lv]
+        return out_score, out_moments
 
     def topk_merge(self, part_dist, part_idx):
         return self.merge_keys(self.pack_keys(part_dist, part_idx))[:2]

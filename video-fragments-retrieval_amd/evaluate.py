@@ -358,3 +358,33 @@ def evaluate_sentences(model, video_iterator, lang_iterator, annotations, device
     if return_topk:
         return out, (dist, idx, rows)
     return out
+
+
+def evaluate_paragraphs(model, video_iterator, lang_iterator, annotations, device, atk=(1, 5, 10, 50), rank=0, world=1,
+                        return_topk=0):
+    """Paragraph-to-video retrieval metrics of the same iterators ``evaluate`` consumes: all sentences of a video together form
+    the query, and the question is which video they describe (the usual video-retrieval protocol on datasets with several
+    descriptions per video).
+
+    The queries of ``lang_iterator`` are grouped by their video with a stable sort (iteration order is kept inside a paragraph):
+    one paragraph per video that has queries, in video order.  The score of (paragraph, video) is the fp32 mean, in sentence order,
+    of the video's best moment distance for each sentence; the 0-based rank of a paragraph is the number of videos whose (score,
+    video index) key sorts before its own video's (``engine.corpus_paragraph_topk``).  Returns ``{"paragraph": {"R@1", "R@5",
+    "R@10", "R@50", "MR"}}`` (``get_metrics``, as ``evaluate_videos``); with ``return_topk`` = k also ``(score, video idx, own
+    video)``: [Ng, k] lists of the k best videos per paragraph and the global video index [Ng] each paragraph belongs to.  A video
+    with more than 64 queries raises ValueError.  Labels, IoU and annotation times play no part."""
+    with _eval_mode(model):
+        ops, _, _, shard, names, Q, own = _prepare(model, video_iterator, lang_iterator, device, rank, world)
+        if shard is None:
+            out = {"paragraph": get_metrics(_empty_metrics(atk))}
+            return (out, (None, None, None)) if return_topk else out
+        order = np.argsort(own, kind="stable")
+        videos, lengths = np.unique(own, return_counts=True)
+        groups = engine.paragraph_groups(lengths=lengths, device=shard.device)
+        Qs = Q[torch.from_numpy(order).to(Q.device)].contiguous()
+        score, vid, ranks, _ = engine.corpus_paragraph_topk(shard, Qs, groups, int(return_topk), videos, ops=ops, world=world)
+        ranks = ranks.cpu().numpy()
+    out = {"paragraph": get_metrics(_rank_metrics(ranks, atk))}
+    if return_topk:
+        return out, (score, vid, videos)
+    return out
