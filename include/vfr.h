@@ -338,6 +338,50 @@ int vfr_score_paragraph_pairs_f32(const float *Q, int64_t Nq, const int64_t *grp
                                   float *out_score, int64_t *out_moments, int *bad, vfr_stream_t stream);
 int vfr_score_paragraphs_stats(const void *workspace, int64_t Nq, int64_t Ng, int Nv, int total_clips, int64_t *stats_host,
                                vfr_stream_t stream);
+/* ---- hard-negative mining for the ranking loss: the training loss IS the retrieval score (F.pairwise_distance(..., eps).mean()
+ * over a span's clips = score(q, video, s, e)), so the hardest negatives of a training span are keys the scorer defines exactly.
+ * items int32 [N, 4] = (query row of Q, CORPUS-GLOBAL video, start_t, end_t): inclusive clip span in utils.generate_moments units.
+ * Items need not be sorted, may repeat and may share query rows; outputs are in the caller's order.
+ *   score(q, v, s, e) = (dist[s] + .. + dist[e]) / (float)(e - s + 1), dist[c] = ||(V[c] - Q[q]) + eps||_2: the canonical chain
+ *           (k-ascending fp32 fma chain, IEEE sqrt, fp32 sum s -> e, one correctly rounded division), BIT-IDENTICAL to what
+ *           vfr_score_moments_f32 writes at [q, moment id of (v, s, e)].
+ *   bad (nullable, device int): set to 1 for an item with query row outside [0, Nq), video < 0, start_t < 0, end_t < start_t (on any
+ *           shard) or end_t >= the video's clip count (on the shard that holds the video); nothing is read or written out of bounds.
+ * vfr_score_spans_f32: out[p] = score of item p.  An item whose video lies outside [vid_base, vid_base + Nv) belongs to another shard
+ *   and is left untouched, as is a malformed one: pre-fill +inf and reduce MIN over shards.  Serves the positives of the miner.
+ * vfr_mine_negatives_f32: an item is a training span (query row, OWN video, positive span).  h >= 0 entries per list:
+ *   inter_dist / inter_vid [Nm,h] (nullable, together): the h smallest keys (fp32 bits of score << 32) | (vid_base + v) over the bank's
+ *           eligible videos v -- global index != the own video and at least end_t + 1 clips -- with score(q, v, start_t, end_t): the
+ *           positive's span applied to the other video, the loss's inter term.  Order (score, global video index) ascending, padded
+ *           with (+inf, -1).  Every shard takes the same items; the lists merge with vfr_topk_merge_f32.
+ *   intra_dist / intra_idx [Nm,h] (nullable, together): the h smallest keys over the eligible moments (s', e') of the own video, id =
+ *           id_base + moment_offsets[v] + position in utils.generate_moments order.  intra_mode VFR_MINE_SAME_LENGTH: e' - s' ==
+ *           end_t - start_t and (s', e') != (start_t, end_t) (CustomBatchSampler, same_length=True); VFR_MINE_ANY: every moment but
+ *           (start_t, end_t) and the spans of excl int32 [Nm, X, 2] (X <= 8 host int, rows padded with (-1, -1); same_length=False:
+ *           none of the annotated spans).  WRITTEN ONLY by the shard that holds the own video (sorted, padded with (+inf, -1)); other
+ *           shards and malformed items leave the rows untouched: pre-fill (+inf, -1) and reduce MIN / MAX over shards.
+ *   floor_dist [Nm] (nullable): an eligible negative with score <= floor_dist[m] is not listed (the positive's own score as the floor:
+ *           semi-hard mining).
+ *   thr_dist [Nm] (nullable) comes with count_inter / count_intra [Nm] int64 (at least one): += the eligible negatives with score <
+ *           thr_dist[m], whatever the floor.  ADDED, so shards chain.  thr = fp32(positive + margin): the number of margin violators.
+ *   A malformed item gives inter padding and adds nothing.  h = 0 with counts only is allowed.  Exact arithmetic only; any D (D = 100
+ *   with 16-byte aligned Q and V takes the register-resident fast path).
+ * Limits: h <= 448, max_clips <= 64, Nm * h < 2^31, vid_base + Nv < 2^32, id_base + total moments < 2^32.  Bad host-side arguments:
+ * VFR_EINVAL before anything is enqueued.
+ * vfr_mine_negatives_workspace_bytes = 256 + 8 h Nm C, C = min(ceil(4096 / Nm), ceil(Nv / 64), 256) >= 1 = the bound on the chunks the
+ * video axis is cut into: O(Nm h), no Nm x Nv term (0 for a bad argument).                                                  */
+#define VFR_MINE_SAME_LENGTH 0
+#define VFR_MINE_ANY 1
+int vfr_score_spans_f32(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, int Nv, int total_clips,
+                        int max_clips, int D, float eps, int64_t vid_base, const int32_t *items, int64_t Np, float *out, int *bad,
+                        vfr_stream_t stream);
+size_t vfr_mine_negatives_workspace_bytes(int64_t Nm, int Nv, int h);
+int vfr_mine_negatives_f32(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, const int64_t *moment_offsets,
+                           int Nv, int total_clips, int max_clips, int D, float eps, int64_t id_base, int64_t vid_base,
+                           const int32_t *items, int64_t Nm, int h, int intra_mode, const int32_t *excl, int X,
+                           const float *floor_dist, const float *thr_dist, float *inter_dist, int64_t *inter_vid, float *intra_dist,
+                           int64_t *intra_idx, int64_t *count_inter, int64_t *count_intra, int *bad, void *workspace,
+                           size_t workspace_bytes, vfr_stream_t stream);
 /* Device self-check of the arithmetic model the pre-filter's margins and the MFMA GEMMs' bit-exactness assume: a
  * v_mfma_f32_16x16x4_f32 = four fp32 fmas, k ascending, on its accumulator (denormals kept).  A, B [16, K] device rows
  * (K % 4 == 0; make them adversarial: wide exponent range, cancellation, denormals): C = A B^T by the matrix pipe against an

@@ -71,6 +71,10 @@ SIGNATURES = {
     "vfr_score_paragraph_pairs_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i64,
                                              _vp, _i64, _vp, _vp, _vp, _vp]),
     "vfr_score_paragraphs_stats": (_i32, [_vp, _i64, _i64, _i32, _i32, ctypes.POINTER(ctypes.c_int64), _vp]),
+    "vfr_score_spans_f32": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "vfr_mine_negatives_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "vfr_mine_negatives_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _i32,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "vfr_topk_pack_keys": (_i32, [_vp, _vp, _i64, _vp, _vp]),
@@ -662,6 +666,121 @@ def score_sentences(S: torch.Tensor, bank: VideoBank, probes: torch.Tensor, k: i
         if R:
             count_lt.index_add_(1, order, cl)
     return od, oi, count_lt
+
+
+def _items(items, who: str) -> torch.Tensor:
+    items = _dev(items, torch.int32, "items")
+    if items.dim() != 2 or items.shape[1] != 4:
+        raise RuntimeError(f"{who}: items must be [N, 4] (query row, video, start_t, end_t), got {tuple(items.shape)}")
+    return items
+
+
+def score_spans(Q: torch.Tensor, bank: VideoBank, items: torch.Tensor, vid_base: int = 0, out: torch.Tensor | None = None,
+                bad: torch.Tensor | None = None, eps: float = 1e-6) -> torch.Tensor:
+    """Scores of named (query, video, span) items (include/vfr.h vfr_score_spans_f32): ``items`` [Np, 4] int32 = (row of ``Q``,
+    corpus-global video, start_t, end_t); the value ``score_moments`` holds at [row, moment id].  Items of videos outside this bank
+    (``vid_base`` .. + its videos) and malformed ones are left untouched: ``out`` [Np] is allocated pre-filled with +inf (or pass
+    another shard's result to chain).  ``bad`` (device int32 [1], nullable) is set to 1 for a malformed item."""
+    Q = _dev(Q, torch.float32, "Q")
+    items = _items(items, "score_spans")
+    if Q.dim() != 2 or Q.shape[1] != bank.dim:
+        raise RuntimeError(f"score_spans: Q must be [Nq, {bank.dim}], got {tuple(Q.shape)}")
+    Np = int(items.shape[0])
+    if out is None:
+        out = torch.full((Np,), float("inf"), dtype=torch.float32, device=Q.device)
+    out = _dev(out, torch.float32, "out")
+    if bad is not None:
+        bad = _dev(bad, torch.int32, "bad")
+    _check(lib().vfr_score_spans_f32(_ptr(Q) if Q.shape[0] else 0, Q.shape[0], bank.emb.data_ptr(), bank.clip_off.data_ptr(),
+                                     bank.num_videos, bank.total_clips, bank.max_clips, bank.dim, eps, int(vid_base),
+                                     _ptr(items) if Np else 0, Np, _ptr(out) if Np else 0, _ptr(bad), _stream()), "vfr_score_spans_f32")
+    return out
+
+
+MINE_MODES = {"same_length": 0, "any": 1}         # include/vfr.h VFR_MINE_SAME_LENGTH / VFR_MINE_ANY
+MINE_MAX_EXCL = 8
+
+
+def mine_negatives(Q: torch.Tensor, bank: VideoBank, items: torch.Tensor, h: int, vid_base: int = 0, intra: str = "same_length",
+                   excl: torch.Tensor | None = None, floor: torch.Tensor | None = None, thr: torch.Tensor | None = None,
+                   want_inter: bool = True, want_intra: bool = True, intra_out=None, count_inter=None, count_intra=None,
+                   bad: torch.Tensor | None = None, workspace: torch.Tensor | None = None, eps: float = 1e-6):
+    """Hard-negative mining (include/vfr.h vfr_mine_negatives_f32): ``items`` [Nm, 4] int32 = (row of ``Q``, own corpus-global video,
+    start_t, end_t) training spans.  Per item the ``h`` hardest inter negatives -- the other videos of this bank with at least
+    end_t + 1 clips, scored at the item's span, as (score, ``vid_base`` + video) -- and the ``h`` hardest intra negatives -- the own
+    video's other moments of the same length (``intra`` "same_length") or all but the item's span and the spans of ``excl``
+    [Nm, X, 2] int32, X <= 8, rows padded with (-1, -1) ("any") -- as (score, global moment id); both padded with (+inf, -1).  The
+    intra lists are written only by the bank that holds the own video: they are allocated pre-filled with padding (or pass another
+    shard's ``intra_out`` = (dist, idx) to chain).  ``floor`` [Nm]: negatives with score <= floor are not listed.  ``thr`` [Nm]:
+    ``count_inter`` / ``count_intra`` [Nm] int64 += the eligible negatives with score < thr (allocated zeroed when None).
+    ``bad`` (device int32 [1], nullable) is set to 1 for a malformed item.  The items are handed to the library sorted by span (stable
+    device sort, no synchronisation), so neighbouring waves read the same clip rows; results come back in the caller's order.
+    Returns (inter_dist, inter_vid, intra_dist, intra_idx, count_inter, count_intra), None for what was not asked for."""
+    if intra not in MINE_MODES:
+        raise RuntimeError(f"mine_negatives: unknown intra mode {intra!r} (same_length, any)")
+    Q = _dev(Q, torch.float32, "Q")
+    items = _items(items, "mine_negatives")
+    if Q.dim() != 2 or Q.shape[1] != bank.dim:
+        raise RuntimeError(f"mine_negatives: Q must be [Nq, {bank.dim}], got {tuple(Q.shape)}")
+    Nm, dev = int(items.shape[0]), Q.device
+    X = 0
+    if excl is not None and intra == "any":
+        excl = _dev(excl, torch.int32, "excl")
+        if excl.dim() != 3 or excl.shape[0] != Nm or excl.shape[2] != 2 or excl.shape[1] > MINE_MAX_EXCL:
+            raise RuntimeError(f"mine_negatives: excl must be [Nm, X <= {MINE_MAX_EXCL}, 2], got {tuple(excl.shape)}")
+        X = int(excl.shape[1])
+    if X == 0:
+        excl = None
+    floor = None if floor is None else _dev(floor, torch.float32, "floor").reshape(Nm)
+    thr = None if thr is None else _dev(thr, torch.float32, "thr").reshape(Nm)
+    if bad is not None:
+        bad = _dev(bad, torch.int32, "bad")
+    lists = h > 0
+    ind = inv = None
+    if want_inter and lists:
+        ind, inv = _out_lists(Nm, h, dev)
+    itd = iti = None
+    if want_intra and lists:
+        if intra_out is None:
+            itd = torch.full((Nm, h), float("inf"), dtype=torch.float32, device=dev)
+            iti = torch.full((Nm, h), -1, dtype=torch.int64, device=dev)
+        else:
+            itd, iti = _dev(intra_out[0], torch.float32, "intra_out[0]"), _dev(intra_out[1], torch.int64, "intra_out[1]")
+    if thr is not None:
+        if want_inter:
+            count_inter = torch.zeros((Nm,), dtype=torch.int64, device=dev) if count_inter is None else _dev(count_inter, torch.int64, "count_inter")
+        if want_intra:
+            count_intra = torch.zeros((Nm,), dtype=torch.int64, device=dev) if count_intra is None else _dev(count_intra, torch.int64, "count_intra")
+        if not (want_inter or want_intra):
+            thr = None
+    else:
+        count_inter = count_intra = None
+    order = None
+    if Nm > 1:                                     # by (start_t, end_t): neighbouring waves then read the same clip rows
+        order = torch.sort(items[:, 2].to(torch.int64) * (1 << 32) + items[:, 3].to(torch.int64), stable=True).indices
+    pick = (lambda t: t) if order is None else (lambda t: None if t is None else t[order].contiguous())
+    zero = (lambda t: t) if order is None else (lambda t: None if t is None else torch.zeros_like(t))
+    s_items, s_excl, s_floor, s_thr = pick(items), pick(excl), pick(floor), pick(thr)
+    s_itd, s_iti = pick(itd), pick(iti)
+    s_ci, s_ca = zero(count_inter), zero(count_intra)
+    nbytes = lib().vfr_mine_negatives_workspace_bytes(Nm, bank.num_videos, h)
+    workspace = _workspace(workspace, nbytes, dev)
+    _check(lib().vfr_mine_negatives_f32(_ptr(Q) if Q.shape[0] else 0, Q.shape[0], bank.emb.data_ptr(), bank.clip_off.data_ptr(),
+                                        bank.mom_off.data_ptr(), bank.num_videos, bank.total_clips, bank.max_clips, bank.dim, eps,
+                                        bank.id_base, int(vid_base), _ptr(s_items) if Nm else 0, Nm, h, MINE_MODES[intra], _ptr(s_excl), X,
+                                        _ptr(s_floor), _ptr(s_thr), _ptr(ind), _ptr(inv), _ptr(s_itd), _ptr(s_iti), _ptr(s_ci),
+                                        _ptr(s_ca), _ptr(bad), workspace.data_ptr(), nbytes, _stream()), "vfr_mine_negatives_f32")
+    if order is not None:                          # back to the caller's order
+        if ind is not None:
+            ind, inv = torch.empty_like(ind).index_copy_(0, order, ind), torch.empty_like(inv).index_copy_(0, order, inv)
+        if itd is not None:
+            itd.index_copy_(0, order, s_itd)
+            iti.index_copy_(0, order, s_iti)
+        if count_inter is not None:
+            count_inter.index_add_(0, order, s_ci)
+        if count_intra is not None:
+            count_intra.index_add_(0, order, s_ca)
+    return ind, inv, itd, iti, count_inter, count_intra
 
 
 def _group_args(Q: torch.Tensor, bank: VideoBank, grp_off: torch.Tensor, max_len: int, eps: float, who: str):

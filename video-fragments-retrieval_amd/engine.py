@@ -78,6 +78,14 @@ class HipOps:
                               bad=None):
         return self.v.score_paragraph_pairs(Q, bank, grp_off, max_len, pairs, vid_base, out_score, out_moments, moments, bad=bad)
 
+    def score_spans(self, Q, bank, items, vid_base=0, out=None, bad=None):
+        return self.v.score_spans(Q, bank, items, vid_base, out, bad=bad)
+
+    def mine_negatives(self, Q, bank, items, h, vid_base=0, intra="same_length", excl=None, floor=None, thr=None, want_inter=True,
+                       want_intra=True, intra_out=None, count_inter=None, count_intra=None, bad=None, workspace=None):
+        return self.v.mine_negatives(Q, bank, items, h, vid_base, intra, excl, floor, thr, want_inter, want_intra, intra_out,
+                                     count_inter, count_intra, bad=bad, workspace=workspace)
+
     def slice_bank(self, bank, counts, v0, v1):
         return self.v.slice_bank(bank, counts, v0, v1)
 
@@ -854,6 +862,93 @@ def corpus_sentence_topk(shard: CorpusShard, S, probes, k, own_sentence=None, op
     return od, oi, (cnt[0] if cnt is not None else None)
 
 
+MINE_MAX_EXCL = 8                         # include/vfr.h: excluded spans per item (VFR_MINE_ANY)
+
+
+@dataclass
+class MinedNegatives:
+    """What ``corpus_mine_negatives`` returns, per item (training span) in the caller's order: ``pos`` [Nm] the positive's score
+    (+inf for an item without one: malformed, or a video of no shard); ``inter_dist`` / ``inter_vid`` [Nm, h] the hardest other
+    videos as (score, global video index); ``intra_dist`` / ``intra_idx`` [Nm, h] the hardest other moments of the own video as
+    (score, global moment id); both padded with (+inf, -1), None for h = 0.  ``count_inter`` / ``count_intra`` [Nm] int64 = the
+    eligible negatives whose score is below positive + margin (None without a margin).  ``bad`` (device int32 [1]) is 1 when some
+    item was malformed (query row or video out of range, start_t < 0, end_t < start_t, end_t past its video): such an item has
+    pos = +inf and padded lists, like one without eligible negatives; ``malformed()`` reads the flag (one synchronisation).
+    ``intra_spans()`` decodes the moment ids on the host."""
+    pos: torch.Tensor
+    inter_dist: torch.Tensor
+    inter_vid: torch.Tensor
+    intra_dist: torch.Tensor
+    intra_idx: torch.Tensor
+    count_inter: torch.Tensor
+    count_intra: torch.Tensor
+    bad: torch.Tensor = None
+    own: np.ndarray = None                 # [Nm] the items' own global video (host)
+    counts_all: np.ndarray = None
+    mom_off_all: np.ndarray = None
+
+    def malformed(self) -> bool:
+        return bool(int(self.bad.item()))
+
+    def intra_spans(self) -> np.ndarray:
+        """[Nm, h, 2] int64 (start_t, end_t) of the intra negatives, (-1, -1) for padding (one device-to-host copy)."""
+        ids = self.intra_idx.cpu().numpy()
+        out = np.full(ids.shape + (2,), -1, np.int64)
+        tables = {}
+        for m in range(ids.shape[0]):
+            real = ids[m] >= 0
+            if not real.any():
+                continue
+            v = int(self.own[m])
+            n = int(self.counts_all[v])
+            if n not in tables:
+                tables[n] = np.asarray(generate_moments(n), np.int64).reshape(-1, 2)
+            out[m, real] = tables[n][ids[m, real] - int(self.mom_off_all[v])]
+        return out
+
+
+def corpus_mine_negatives(shard: CorpusShard, Q, items, h, intra="same_length", excl=None, semi_hard=False, margin=None, ops=None,
+                          world=1, workspace=None) -> MinedNegatives:
+    """Hard-negative mining over the corpus for the ranking loss: ``items`` (host array-like [Nm, 4]) = (row of ``Q``, own global
+    video, start_t, end_t) training spans.  The loss's terms are retrieval scores, so the hardest negatives are exact keys: per item
+    the ``h`` other videos (of at least end_t + 1 clips) with the smallest score at the item's span, and the ``h`` other moments of
+    the own video -- of the same length (``intra`` "same_length") or all but the item's span and the spans of ``excl`` [Nm, X <= 8, 2]
+    ("any") -- with the smallest score.  ``semi_hard``: only negatives scoring above the positive.  ``margin``: also the numbers of
+    inter / intra negatives below fp32(positive + margin), the margin violators.  Order: the positives' scores (one launch on the
+    rank that holds the video, MIN-reduced), floor and threshold from them, one mining call, then the sharded tail: inter lists
+    merged by key, intra lists MIN / MAX-merged (only the own video's rank writes them), counts summed."""
+    ops = ops or HipOps()
+    if intra not in ("same_length", "any"):
+        raise ValueError(f"corpus_mine_negatives: unknown intra mode {intra!r} (same_length, any)")
+    it = np.asarray(items.cpu() if isinstance(items, torch.Tensor) else items, np.int64).reshape(-1, 4)
+    Nm, dev = len(it), shard.device
+    items_t = torch.from_numpy(it.astype(np.int32)).to(dev)
+    excl_t = None
+    if excl is not None and intra == "any":
+        ex = np.asarray(excl.cpu() if isinstance(excl, torch.Tensor) else excl, np.int64)
+        if ex.ndim != 3 or ex.shape[0] != Nm or ex.shape[2] != 2 or ex.shape[1] > MINE_MAX_EXCL:
+            raise ValueError(f"corpus_mine_negatives: excl must be [Nm, X <= {MINE_MAX_EXCL}, 2], got {ex.shape}")
+        excl_t = torch.from_numpy(ex.astype(np.int32)).to(dev)
+    dist = _group(world)
+    bad = torch.zeros((1,), dtype=torch.int32, device=dev)
+    pos = ops.score_spans(Q, shard.bank, items_t, shard.lo, bad=bad)
+    if dist is not None:
+        dist.all_reduce(pos, op=dist.ReduceOp.MIN)
+    floor = pos if semi_hard else None
+    thr = None if margin is None else pos + torch.full_like(pos, float(margin))          # fp32(pos + fp32(margin))
+    ind, inv, itd, iti, ci, ca = ops.mine_negatives(Q, shard.bank, items_t, h, shard.lo, intra, excl_t, floor, thr, bad=bad,
+                                                    workspace=workspace)
+    if dist is not None:
+        dist.all_reduce(bad, op=dist.ReduceOp.MAX)             # end_t past the video is seen by the owning rank only
+        ind, inv, ci = _exchange(ind, inv, ci, h, ops, world)
+        if h > 0:
+            dist.all_reduce(itd, op=dist.ReduceOp.MIN)
+            dist.all_reduce(iti, op=dist.ReduceOp.MAX)
+        if ca is not None:
+            dist.all_reduce(ca, op=dist.ReduceOp.SUM)
+    return MinedNegatives(pos, ind, inv, itd, iti, ci, ca, bad, it[:, 1].copy(), shard.counts_all, shard.mom_off_all)
+
+
 PARAGRAPH_MAX_LEN = 64                    # include/vfr.h: sentences per paragraph
 
 
@@ -1303,6 +1398,109 @@ class TorchCpuOps:
             out[m] = _pack_key(acc / float(e0 - s0 + 1), ids)
         kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nm), rank_idx.reshape(-1, Nm))
         return self._topk_lists(out, k) + (self._counts_below(out, kstar, count_lt),)
+
+    def _span_scores(self, Q, bank, items, vid_base, bad, eps=1e-6):
+        """What the mining entry points share: the items as host rows with their malformed flag and own local video, and the clip
+        distances of every distinct query row against the bank ([U, C], the provider's one distance)."""
+        rows = [[int(x) for x in r] for r in torch.as_tensor(items).tolist()]
+        off = bank.clip_off.tolist()
+        Nv, Nq = len(off) - 1, Q.shape[0]
+        out = []
+        for q, gv, s0, e0 in rows:
+            wrong = q < 0 or q >= Nq or gv < 0 or s0 < 0 or e0 < s0
+            lv = gv - vid_base
+            owned = gv >= 0 and 0 <= lv < Nv
+            if owned and e0 >= off[lv + 1] - off[lv]:
+                wrong = True
+            if wrong and bad is not None:
+                bad.fill_(1)
+            out.append((q, gv, s0, e0, wrong, lv if owned else -1))
+        used = sorted({r[0] for r in out if not r[4]})
+        slot = {q: i for i, q in enumerate(used)}
+        d = self._clip_dist(Q.float()[used], bank.emb, eps) if used else torch.zeros((0, bank.emb.shape[0]))
+        return out, off, slot, d
+
+    def score_spans(self, Q, bank, items, vid_base=0, out=None, bad=None):
+        """Named (query, global video, span) scores (same semantics as ``_vfr.score_spans``): the fp32 chain s -> e of the clip
+        distances and one division; items of other shards and malformed ones are left untouched (+inf pre-filled)."""
+        rows, off, slot, d = self._span_scores(Q, bank, items, vid_base, bad)
+        if out is None:
+            out = torch.full((len(rows),), float("inf"))
+        for p, (q, gv, s0, e0, wrong, lv) in enumerate(rows):
+            if wrong or lv < 0:
+                continue
+            acc = d[slot[q], off[lv] + s0]
+            for c in range(s0 + 1, e0 + 1):
+                acc = acc + d[slot[q], off[lv] + c]
+            out[p] = acc / float(e0 - s0 + 1)
+        return out
+
+    def mine_negatives(self, Q, bank, items, h, vid_base=0, intra="same_length", excl=None, floor=None, thr=None, want_inter=True,
+                       want_intra=True, intra_out=None, count_inter=None, count_intra=None, bad=None, workspace=None):
+        """Hard-negative mining from dense torch arithmetic (same semantics and bits as ``_vfr.mine_negatives``): per item the keys
+        (score at the item's span, vid_base + video) of the other videos with at least end_t + 1 clips, the keys (score, global
+        moment id) of the own video's eligible moments, the ``h`` smallest above the floor, and the eligible keys below ``thr``."""
+        if intra not in ("same_length", "any"):
+            raise RuntimeError(f"mine_negatives: unknown intra mode {intra!r} (same_length, any)")
+        rows, off, slot, d = self._span_scores(Q, bank, items, vid_base, bad)
+        Nm = len(rows)
+        offs = np.asarray(off, np.int64)
+        n_all = np.diff(offs)
+        mo = csr_offsets(n_all)[1]
+        vids = vid_base + torch.arange(len(n_all))
+        ex = None if excl is None or intra != "any" else torch.as_tensor(excl).tolist()
+        lists = h > 0
+        ind = inv = itd = iti = None
+        if want_inter and lists:
+            ind, inv = torch.full((Nm, h), float("inf")), torch.full((Nm, h), -1, dtype=torch.int64)
+        if want_intra and lists:
+            itd, iti = (torch.full((Nm, h), float("inf")), torch.full((Nm, h), -1, dtype=torch.int64)) if intra_out is None else intra_out
+        if thr is None or not (want_inter or want_intra):
+            thr = count_inter = count_intra = None
+        else:
+            count_inter = (torch.zeros(Nm, dtype=torch.int64) if count_inter is None else count_inter) if want_inter else None
+            count_intra = (torch.zeros(Nm, dtype=torch.int64) if count_intra is None else count_intra) if want_intra else None
+
+        def select(m, sc, ids):
+            """(listed keys sorted and padded as lists, number below the threshold) of the eligible (score, id) pairs"""
+            below = int((sc < thr[m]).sum()) if thr is not None else 0
+            if floor is not None:
+                keep = ~(sc <= floor[m])
+                sc, ids = sc[keep], ids[keep]
+            return self._topk_lists(_pack_key(sc, ids)[None], h) if lists else (None, None), below
+
+        for m, (q, gv, s0, e0, wrong, lv) in enumerate(rows):
+            if wrong:
+                continue
+            dq = d[slot[q]]
+            if want_inter:
+                el = np.flatnonzero((n_all > e0) & (np.arange(len(n_all)) != gv - vid_base))
+                base = torch.from_numpy(offs[el])
+                acc = dq[base + s0]
+                for c in range(s0 + 1, e0 + 1):
+                    acc = acc + dq[base + c]
+                (ld, li), below = select(m, acc / float(e0 - s0 + 1), vids[torch.from_numpy(el)])
+                if lists:
+                    ind[m], inv[m] = ld[0], li[0]
+                if count_inter is not None:
+                    count_inter[m] += below
+            if want_intra and lv >= 0:
+                n = int(n_all[lv])
+                spans = generate_moments(n)
+                sc = self._video_scores(dq[None, off[lv]:off[lv + 1]])[0]
+                if intra == "same_length":
+                    ok = [e1 - s1 == e0 - s0 and (s1, e1) != (s0, e0) for s1, e1 in spans]
+                else:
+                    gone = {(s0, e0)} | ({(int(a), int(b)) for a, b in ex[m]} if ex is not None else set())
+                    ok = [(s1, e1) not in gone for s1, e1 in spans]
+                ok = torch.tensor(ok, dtype=torch.bool)
+                ids = bank.id_base + int(mo[lv]) + torch.arange(len(spans))
+                (ld, li), below = select(m, sc[ok], ids[ok])
+                if lists:
+                    itd[m], iti[m] = ld[0], li[0]
+                if count_intra is not None:
+                    count_intra[m] += below
+        return ind, inv, itd, iti, count_inter, count_intra
 
     def _video_best_keys(self, Q, bank):
         """[Nq, Nv] packed (distance, global moment id) best key of every video for every row of ``Q`` (KEY_INF: no clips)."""

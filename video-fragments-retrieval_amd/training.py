@@ -143,6 +143,120 @@ class TripletBatchSampler(BatchSampler):
             yield batch
 
 
+class HardNegativeSampler(TripletBatchSampler):
+    """``TripletBatchSampler`` whose two negatives come from the retrieval engine: the ranking loss's terms are retrieval scores,
+    so the hardest intra segment and inter video of a training span are exact keys (``engine.corpus_mine_negatives``).
+
+    Before the first ``refresh`` it makes exactly the parent's draws (the same ``random`` state gives the parent's batches).
+    ``refresh`` encodes the corpus and the sentences with the current model and mines, per (annotation, distinct annotated span
+    inside its video), the ``h`` hardest negatives of each kind.  Afterwards ``__iter__`` is the parent's loop except for the two
+    negative draws: with probability ``hard_fraction`` the intra segment and the inter video are drawn from the mined lists
+    (``random.choice`` when ``train``, else entry 0 = the hardest); an empty mined list falls back to the parent's draw.  Where the
+    parent has no candidate either (a span that covers its whole video has no same-length neighbour) the any-length rule supplies
+    the intra segment, and an annotation whose video has no other moment at all is left out of the epoch.
+    ``last_stats``: items mined, the margin violators (with ``margin``), the draws taken from the mined lists / the parent, and
+    ``skipped`` = the annotations left out of the last epoch."""
+
+    def __init__(self, batch_size, annotations, num_segments_info, train=True, drop_last=False, same_length=True, h=16,
+                 hard_fraction=1.0):
+        super().__init__(batch_size, annotations, num_segments_info, train, drop_last, same_length)
+        self.h = int(h)
+        self.hard_fraction = float(hard_fraction)
+        self.mined = None            # (annot_id, start_t, end_t) -> (inter video names, intra spans), hardest first
+        self.last_stats = {}
+
+    def refresh(self, model, dataset, device, ops=None, semi_hard=False, margin=None):
+        """Mine with the current ``model`` (eval mode for the encoders, the caller's mode restored): one corpus encode, one sentence
+        encode, one ``engine.corpus_mine_negatives``; the results are kept as host tables."""
+        from . import engine
+        from .evaluate import _eval_mode
+        ops = ops or engine.ops_for(device)
+        bank = dataset.feature_bank()
+        index = {v: i for i, v in enumerate(bank.videos)}
+        annot_ids = list(self.annotations.keys())
+        with _eval_mode(model), torch.no_grad():
+            shard = engine.build_corpus(model, bank, device, ops)
+            tokens = torch.cat([torch.as_tensor(dataset.lang_features[a]).reshape(1, -1) for a in annot_ids]) if annot_ids else None
+            Q = engine.encode_queries(model, tokens, device, ops) if annot_ids else None
+        rows, keys, excl = [], [], []
+        for r, a in enumerate(annot_ids):
+            info = self.annotations[a]
+            n = self.num_segments_info[info["video"]]
+            named = sorted({(int(s), int(e)) for s, e in info["times"]})
+            if not self.same_length and len(named) > engine.MINE_MAX_EXCL:
+                continue                                   # more annotated spans than the kernel excludes: the parent's draws
+            for s, e in dict.fromkeys(self._positive_spans(a)):
+                if 0 <= s <= e < n:
+                    rows.append((r, index[info["video"]], s, e))
+                    keys.append((a, s, e))
+                    excl.append(named)
+        self.mined = {}
+        self.last_stats = dict(items=len(rows), mined_draws=0, parent_draws=0, skipped=0)
+        if not rows or self.h <= 0:
+            return self
+        ex = None
+        if not self.same_length:
+            X = max(len(x) for x in excl)
+            ex = np.full((len(rows), X, 2), -1, np.int64)
+            for i, x in enumerate(excl):
+                ex[i, :len(x)] = x
+        res = engine.corpus_mine_negatives(shard, Q, np.asarray(rows, np.int64), self.h, "same_length" if self.same_length else "any",
+                                           ex, semi_hard, margin, ops)
+        vids, spans = res.inter_vid.cpu().numpy(), res.intra_spans()
+        for i, key in enumerate(keys):
+            self.mined[key] = ([bank.videos[v] for v in vids[i] if v >= 0], [(int(s), int(e)) for s, e in spans[i] if s >= 0])
+        if margin is not None:
+            self.last_stats.update(violators_inter=int(res.count_inter.sum()), violators_intra=int(res.count_intra.sum()))
+        return self
+
+    def __iter__(self):
+        if self.mined is None:
+            yield from super().__iter__()
+            return
+        stats = self.last_stats
+        stats["mined_draws"] = stats["parent_draws"] = stats["skipped"] = 0
+        pick = random.choice if self.train else (lambda seq: seq[0])
+        annotation_ids = list(self.annotations.keys())
+        if self.train:
+            random.shuffle(annotation_ids)
+        batch = []
+        posit_batch_size, intra_batch_size = 0, 0
+        for annot_id in annotation_ids:
+            annot_info = self.annotations[annot_id]
+            video = annot_info["video"]
+            num_segments = self.num_segments_info[video]
+            spans = self._positive_spans(annot_id)
+            if self.train:
+                start_t, end_t = random.choice(spans)
+            else:
+                start_t, end_t = Counter(spans).most_common()[0][0]
+            hard = self.hard_fraction > 0 and (self.hard_fraction >= 1 or random.random() < self.hard_fraction)
+            inter, intra = self.mined.get((annot_id, start_t, end_t), ((), ())) if hard else ((), ())
+            if intra:
+                start_tn, end_tn = pick(intra)
+            else:
+                possible_segments = self._intra_candidates(annot_info, num_segments, start_t, end_t)
+                if not possible_segments and self.same_length:          # no same-length neighbour: any other moment
+                    possible_segments = [m for m in generate_moments(num_segments) if m != (start_t, end_t)]
+                if not possible_segments:
+                    stats["skipped"] += 1
+                    continue
+                start_tn, end_tn = pick(possible_segments)
+            video_neg = pick(inter) if inter else self._inter_negative(video, end_t + 1)
+            stats["mined_draws"] += bool(intra) + bool(inter)
+            stats["parent_draws"] += (not intra) + (not inter)
+            batch.append(dict(annotation_id=annot_id, video_pos=video, video_neg=video_neg, start_t=start_t, end_t=end_t,
+                              start_tn=start_tn, end_tn=end_tn))
+            posit_batch_size += end_t - start_t + 1
+            intra_batch_size += end_tn - start_tn + 1
+            if max(posit_batch_size, intra_batch_size) >= self.batch_size:
+                yield batch
+                batch = []
+                posit_batch_size, intra_batch_size = 0, 0
+        if len(batch) > 0 and not self.drop_last:
+            yield batch
+
+
 def custom_collate(batch):
     """``model/data.py:346-356`` for host tensors: samples with posit / intra / inter / lang -> one batch dict."""
     posit, intra, inter, lang, mask_posit, mask_intra = [], [], [], [], [], []
