@@ -382,6 +382,46 @@ int vfr_mine_negatives_f32(const float *Q, int64_t Nq, const float *V, const int
                            const float *floor_dist, const float *thr_dist, float *inter_dist, int64_t *inter_vid, float *intra_dist,
                            int64_t *intra_idx, int64_t *count_inter, int64_t *count_intra, int *bad, void *workspace,
                            size_t workspace_bytes, vfr_stream_t stream);
+/* ---- late-fusion retrieval: rank by a weighted sum over S streams (two feature extractors, RGB + flow, several seeds) that describe
+ * the SAME videos: one clip_offsets / moment_offsets, per stream s a clip bank V_s [total_clips, D_s], a query matrix Q_s [Nq, D_s]
+ * and a weight w_s (fp32, finite, >= 0).  The streams are HOST arrays of S device pointers / widths / weights (Q_host, V_host,
+ * D_host, w_host), handed to the kernels by value like vfr_adam_step_f32's pointer arrays; 1 <= S <= VFR_FUSION_MAX_STREAMS.
+ *   stream clip distance  d_s[q, c] = ||(V_s[c] - Q_s[q]) + eps||_2, the canonical chain: the bits of vfr_score_moments_f32 on
+ *           stream s at the single-clip moment (c, c).
+ *   fused clip distance   f = fl(w_0 d_0); f = fl(f + fl(w_s d_s)) for s = 1 .. S-1: fp32, every operation rounded, no fma.
+ *   fused moment score    the moment chain on f: sequential fp32 sum of f[s..e] started at f[s], one IEEE division by
+ *           (float)(e - s + 1), utils.generate_moments order.  (In real arithmetic: the weighted sum of the per-stream moment
+ *           scores -- the mean is linear -- with one triangle per (query, video), not S.)
+ *   keys    (fused score, id_base + moment_offsets[v] + j) ascending, padding (+inf, -1), as vfr_score_topk_f32.
+ * S = 1 with w = (1), and w = (1, 0, ..) for any S (finite distances), give vfr_score_topk_f32 / vfr_score_video_topk_f32
+ * (VFR_SCORE_EXACT) on stream 0 BIT FOR BIT.
+ * vfr_score_fusion_own_f32: each query against ONE video own[q] (local index; outside [0, Nv): the row is all +inf): fused scores
+ *   [Nq, Mmax], tail +inf -- layout and meaning of vfr_score_own_f32, so the rows feed vfr_gt_best_keys_f32 / vfr_gt_rank_keys_f32.
+ * vfr_score_fusion_f32: level VFR_FUSION_MOMENTS: out_dist / out_idx [Nq,k] = the k smallest keys over all moments; count_lt[r][q]
+ *   += the moments whose key sorts strictly before (rank_dist[r][q], rank_idx[r][q]).  VFR_FUSION_VIDEOS: the k smallest BEST
+ *   keys of the videos (the whole triangle decides a video's best key) as (best score, id of the best moment); count_lt[r][q] +=
+ *   the videos whose best key sorts before the rank key.  num_rank <= 4, counts are ADDED (shards chain; lists merge with
+ *   vfr_topk_merge_f32); k = 0 with counts only is allowed.  min_clips is accepted for the shared argument list and unused.
+ * Limits: max_clips <= 64, k <= 448, id_base + total moments < 2^32, Nq * k < 2^31, and the query rows of all streams must fit the
+ * kernels' LDS plan: sum over s of round_up(D_s, 4) <= VFR_FUSION_MAX_SUM_D (32 KB of rows + 16 KB of clip distances + 4 KB of keys
+ * in a 64 KB workgroup), VFR_EUNSUPPORTED above it.  VFR_EINVAL before anything is enqueued for S outside 1 .. 4, a null stream
+ * array or stream pointer, D_s < 1, a weight that is negative, NaN or infinite, and the other bad host-side arguments.  Exact
+ * arithmetic only (no MFMA bounds pre-filter: per-stream margins would have to be combined through the weighted sum).
+ * vfr_score_fusion_workspace_bytes = 256 + 8 k Nq C, C = min(ceil(4096 / Nq), ceil(Nv / 64), 256) >= 1 = the bound on the chunks the
+ * video axis is cut into: O(Nq k), no Nq x Nv term (0 for a bad argument).                                                   */
+#define VFR_FUSION_MAX_STREAMS 4
+#define VFR_FUSION_MAX_SUM_D 8192
+#define VFR_FUSION_MOMENTS 0
+#define VFR_FUSION_VIDEOS 1
+int vfr_score_fusion_own_f32(const float *const *Q_host, const float *const *V_host, const int *D_host, const float *w_host, int S,
+                             int64_t Nq, const int32_t *clip_offsets, const int32_t *own, int Nv, int max_clips, float eps, int Mmax,
+                             float *scores, vfr_stream_t stream);
+size_t vfr_score_fusion_workspace_bytes(int64_t Nq, int Nv, int k);
+int vfr_score_fusion_f32(const float *const *Q_host, const float *const *V_host, const int *D_host, const float *w_host, int S,
+                         int64_t Nq, const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv, int total_clips,
+                         int min_clips, int max_clips, float eps, int64_t id_base, int level, int k, float *out_dist,
+                         int64_t *out_idx, int num_rank, const float *rank_dist, const int64_t *rank_idx, int64_t *count_lt,
+                         void *workspace, size_t workspace_bytes, vfr_stream_t stream);
 /* Device self-check of the arithmetic model the pre-filter's margins and the MFMA GEMMs' bit-exactness assume: a
  * v_mfma_f32_16x16x4_f32 = four fp32 fmas, k ascending, on its accumulator (denormals kept).  A, B [16, K] device rows
  * (K % 4 == 0; make them adversarial: wide exponent range, cancellation, denormals): C = A B^T by the matrix pipe against an

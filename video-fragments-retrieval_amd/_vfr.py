@@ -75,6 +75,10 @@ SIGNATURES = {
     "vfr_mine_negatives_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "vfr_mine_negatives_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _i32,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vfr_score_fusion_own_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp]),
+    "vfr_score_fusion_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "vfr_score_fusion_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _i32, _vp, _vp,
+                                    _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "vfr_topk_pack_keys": (_i32, [_vp, _vp, _i64, _vp, _vp]),
@@ -622,6 +626,103 @@ def score_subset(Q: torch.Tensor, bank: VideoBank, cand_off: torch.Tensor, cand_
                                       int(max_list), lv, k,
                                       _ptr(od), _ptr(oi), R, _ptr(rank_dist), _ptr(rank_idx), _ptr(count_lt), _ptr(bad),
                                       workspace.data_ptr(), nbytes, _stream()), "vfr_score_subset_f32")
+    return od, oi, count_lt
+
+
+FUSION_LEVELS = {"moments": 0, "videos": 1}   # include/vfr.h VFR_FUSION_MOMENTS / VFR_FUSION_VIDEOS
+FUSION_MAX_STREAMS = 4                        # include/vfr.h VFR_FUSION_MAX_STREAMS
+
+
+def fusion_weights(weights, S: int) -> np.ndarray:
+    """The stream weights of a late fusion as fp32 [S]: one per stream, finite, >= 0 (ValueError otherwise).  Host only."""
+    w = np.asarray(list(weights), dtype=np.float64).reshape(-1)
+    if not 1 <= S <= FUSION_MAX_STREAMS:
+        raise ValueError(f"late fusion takes 1 .. {FUSION_MAX_STREAMS} streams, got {S}")
+    if len(w) != S:
+        raise ValueError(f"late fusion: {len(w)} weights for {S} streams")
+    w32 = w.astype(np.float32)
+    if not (np.all(np.isfinite(w32)) and np.all(w32 >= 0)):
+        raise ValueError(f"late fusion: weights must be finite and >= 0, got {w.tolist()}")
+    return w32
+
+
+def _same_clip_off(b: VideoBank, b0: VideoBank) -> bool:
+    """Do two banks hold the same clip offsets?  Banks that own a tensor each are compared on the device ONCE (a host
+    synchronisation); the answer is kept on ``b`` for as long as neither tensor is replaced or edited in place."""
+    if b.clip_off.data_ptr() == b0.clip_off.data_ptr():
+        return True
+    token = (b0.clip_off.data_ptr(), b0.clip_off._version, b.clip_off.data_ptr(), b.clip_off._version)
+    if getattr(b, "_fusion_same", None) != token:
+        if not torch.equal(b.clip_off, b0.clip_off):
+            return False
+        b._fusion_same = token
+    return True
+
+
+def _fusion_streams(Qs, banks, weights, who: str):
+    """The stream description both fusion entry points take: the checked tensors and the four host arrays (device pointers of the
+    query matrices and clip banks, widths, weights).  The banks must describe the same videos on one device."""
+    Qs, banks = list(Qs), list(banks)
+    if len(Qs) != len(banks):
+        raise ValueError(f"{who}: {len(Qs)} query matrices for {len(banks)} banks")
+    w = fusion_weights(weights, len(banks))
+    Qs = [_dev(Q, torch.float32, f"Qs[{s}]") for s, Q in enumerate(Qs)]
+    b0 = banks[0]
+    for s, (Q, b) in enumerate(zip(Qs, banks)):
+        if Q.dim() != 2 or Q.shape[1] != b.dim or Q.shape[0] != Qs[0].shape[0]:
+            raise ValueError(f"{who}: Qs[{s}] must be [{Qs[0].shape[0]}, {b.dim}], got {tuple(Q.shape)}")
+        if Q.device != b.emb.device or b.emb.device != b0.emb.device:
+            raise ValueError(f"{who}: stream {s} lives on another device")
+        if b is not b0 and (b.id_base != b0.id_base or b.num_videos != b0.num_videos or b.total_clips != b0.total_clips or
+                            not _same_clip_off(b, b0)):
+            raise ValueError(f"{who}: bank {s} does not describe the videos of bank 0 (clip_off, id_base)")
+    S = len(banks)
+    hosts = ((ctypes.c_void_p * S)(*[Q.data_ptr() for Q in Qs]), (ctypes.c_void_p * S)(*[b.emb.data_ptr() for b in banks]),
+             (ctypes.c_int * S)(*[b.dim for b in banks]), (ctypes.c_float * S)(*w.tolist()), S)
+    return Qs, banks, hosts
+
+
+def score_fusion_own(Qs, banks, weights, own: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+    """Late-fusion scores of each query against ONE video ``own[q]`` (include/vfr.h vfr_score_fusion_own_f32): [Nq, Mmax] fused
+    moment scores in ``utils.generate_moments`` order, tail +inf -- the layout of ``score_own``, so ``gt_best_keys`` /
+    ``gt_rank_keys`` take it.  ``Qs`` / ``banks`` / ``weights``: one query matrix [Nq, D_s], one ``VideoBank`` of the same videos
+    and one weight (finite, >= 0) per stream."""
+    Qs, banks, hosts = _fusion_streams(Qs, banks, weights, "score_fusion_own")
+    b0 = banks[0]
+    own = _dev(own, torch.int32, "own")
+    Nq = Qs[0].shape[0]
+    if own.numel() != Nq:
+        raise ValueError(f"score_fusion_own: {own.numel()} own videos for {Nq} queries")
+    Mmax = b0.max_clips * (b0.max_clips + 1) // 2
+    out = torch.empty((Nq, Mmax), dtype=torch.float32, device=Qs[0].device)
+    _check(lib().vfr_score_fusion_own_f32(*hosts, Nq, b0.clip_off.data_ptr(), _ptr(own) if Nq else 0, b0.num_videos, b0.max_clips, eps,
+                                          Mmax, out.data_ptr() if out.numel() else 0, _stream()), "vfr_score_fusion_own_f32")
+    return out
+
+
+def score_fusion(Qs, banks, weights, k: int, level: str = "moments", rank_dist=None, rank_idx=None, count_lt=None,
+                 workspace: torch.Tensor | None = None, eps: float = 1e-6):
+    """Late-fusion retrieval (include/vfr.h vfr_score_fusion_f32): moments ranked by the weighted sum over S <= 4 streams.  ``Qs``:
+    one query matrix [Nq, D_s] per stream; ``banks``: one ``VideoBank`` per stream over the SAME videos (equal device, ``clip_off``
+    and ``id_base``, else ValueError); ``weights``: one finite weight >= 0 per stream.  The fused clip distance is
+    fl(.. fl(fl(w_0 d_0) + fl(w_1 d_1)) ..) and the moment chain runs on it.  ``level`` "moments": the k best moments; "videos":
+    the k best videos as (best fused score, best moment id).  Padded with (+inf, -1).  rank_dist / rank_idx [R, Nq] (or [Nq]),
+    R <= 4: ``count_lt`` [R, Nq] int64 += the moments (videos) that sort before each rank key (allocated zeroed when None).
+    Returns (dist [Nq,k] | None, idx [Nq,k] int64 | None, count_lt | None)."""
+    if level not in FUSION_LEVELS:
+        raise ValueError(f"score_fusion: unknown level {level!r} (moments, videos)")
+    Qs, banks, hosts = _fusion_streams(Qs, banks, weights, "score_fusion")
+    b0 = banks[0]
+    Nq, dev = Qs[0].shape[0], Qs[0].device
+    od, oi = _out_lists(Nq, k, dev)
+    rank_dist, rank_idx, count_lt, R = _rank_keys(rank_dist, rank_idx, count_lt, Nq, dev)
+    nbytes = lib().vfr_score_fusion_workspace_bytes(Nq, b0.num_videos, k)
+    workspace = _workspace(workspace, nbytes, dev)
+    workspace._vfr_bank = None                   # whatever a pre-filter left in this workspace is overwritten
+    _check(lib().vfr_score_fusion_f32(*hosts, Nq, b0.clip_off.data_ptr(), b0.mom_off.data_ptr(), b0.num_videos, b0.total_clips,
+                                      b0.min_clips, b0.max_clips, eps, b0.id_base, FUSION_LEVELS[level], k, _ptr(od), _ptr(oi), R,
+                                      _ptr(rank_dist), _ptr(rank_idx), _ptr(count_lt), workspace.data_ptr(), nbytes, _stream()),
+           "vfr_score_fusion_f32")
     return od, oi, count_lt
 
 

@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ._vfr import KEY_EMPTY as KEY_INF, csr_offsets   # (does not load libvfr.so)  KEY_INF = key of (+inf, max id): "no positive moment here"
+from ._vfr import KEY_EMPTY as KEY_INF, csr_offsets, fusion_weights   # (does not load libvfr.so)  KEY_INF = key of (+inf, max id): "no positive moment here"
 from .utils import generate_moments, get_iou
 
 
@@ -85,6 +85,12 @@ class HipOps:
                        want_intra=True, intra_out=None, count_inter=None, count_intra=None, bad=None, workspace=None):
         return self.v.mine_negatives(Q, bank, items, h, vid_base, intra, excl, floor, thr, want_inter, want_intra, intra_out,
                                      count_inter, count_intra, bad=bad, workspace=workspace)
+
+    def score_fusion(self, Qs, banks, weights, k, level="moments", rank_dist=None, rank_idx=None, count_lt=None, workspace=None):
+        return self.v.score_fusion(Qs, banks, weights, k, level, rank_dist, rank_idx, count_lt=count_lt, workspace=workspace)
+
+    def score_fusion_own(self, Qs, banks, weights, own_local):
+        return self.v.score_fusion_own(Qs, banks, weights, own_local)
 
     def slice_bank(self, bank, counts, v0, v1):
         return self.v.slice_bank(bank, counts, v0, v1)
@@ -825,6 +831,98 @@ def corpus_subset_topk(shard: CorpusShard, Q, k, lists: CandidateLists, level="m
     return od, oi, vid, cnt
 
 
+@dataclass
+class FusedCorpus:
+    """S streams of the SAME videos for late fusion (``fuse_corpora``): one ``CorpusShard`` per stream -- each stream's own clip
+    embeddings, of its own width -- and the fp32 stream weights."""
+    shards: list
+    weights: np.ndarray          # fp32 [S], finite, >= 0
+    names: object = None         # the corpus' video names (when given)
+
+    @property
+    def first(self) -> CorpusShard:
+        return self.shards[0]
+
+    @property
+    def banks(self):
+        return [s.bank for s in self.shards]
+
+
+def fuse_corpora(shards, weights, names=None) -> FusedCorpus:
+    """S ``CorpusShard``s (1 <= S <= 4) of the same videos + one weight per stream -> ``FusedCorpus``.  ValueError when the streams do
+    not describe the same corpus: different clip counts, a different shard range, a weight that is negative, NaN or infinite, or
+    (``names``: one list of video names per stream) a different video order."""
+    shards = list(shards)
+    w = fusion_weights(weights, len(shards))
+    a = shards[0]
+    for s, b in enumerate(shards[1:], 1):
+        if not np.array_equal(np.asarray(a.counts_all), np.asarray(b.counts_all)):
+            raise ValueError(f"fuse_corpora: stream {s} has other clip counts than stream 0")
+        if (a.lo, a.hi) != (b.lo, b.hi):
+            raise ValueError(f"fuse_corpora: stream {s} holds videos [{b.lo}, {b.hi}), stream 0 [{a.lo}, {a.hi})")
+        if torch.device(a.device) != torch.device(b.device):
+            raise ValueError(f"fuse_corpora: stream {s} lives on {b.device}, stream 0 on {a.device}")
+    if names is not None:
+        names = [list(n) for n in names]
+        if len(names) != len(shards):
+            raise ValueError(f"fuse_corpora: {len(names)} name lists for {len(shards)} streams")
+        for s, n in enumerate(names[1:], 1):
+            if n != names[0]:
+                raise ValueError(f"fuse_corpora: stream {s} iterates the videos in another order than stream 0")
+        names = names[0]
+    return FusedCorpus(shards, w, names)
+
+
+def corpus_fusion_topk(fused: FusedCorpus, Qs, k, level="moments", own_global=None, labels=None, ops=None, world=1, workspace=None):
+    """Late-fusion retrieval over the corpus: moments ranked by the weighted sum over the streams of ``fused`` (``fuse_corpora``),
+    ``Qs`` = one query matrix per stream.  ``level`` "moments": the k best moments; "videos": the k best videos, each as its best
+    moment.  Every rank scores its shard of every stream; a video never spans shards, so the lists merge with the moment-key merge
+    and the counts add.
+    Ground truth: "moments" with ``own_global`` and ``labels`` [R, Nq, Mmax] (``gt_labels``) -> ranks [R, Nq] = 0-based position of
+    the best positive moment in the fused order (IndexError for a query without a positive moment, as ``corpus_ranks``); "videos"
+    with ``own_global`` -> ranks [Nq] = videos whose best fused key sorts before the own video's.  Own fused scores go through the
+    GT key functions ``corpus_ranks`` uses.
+    Returns (dist [Nq,k], moment id [Nq,k] int64, video index [Nq,k] int64 (-1 = padding), ranks | None); lists are None for k = 0."""
+    ops = ops or HipOps()
+    if level not in ("moments", "videos"):
+        raise ValueError(f"corpus_fusion_topk: unknown level {level!r} (moments, videos)")
+    Qs = list(Qs)
+    if len(Qs) != len(fused.shards):
+        raise ValueError(f"corpus_fusion_topk: {len(Qs)} query matrices for {len(fused.shards)} streams")
+    shard, banks = fused.first, fused.banks
+    Nq = Qs[0].shape[0]
+    gt = None
+    if own_global is not None and level == "videos":
+        idx = gt_index(shard, own_global)
+        if idx.sel is not None and idx.Mloc > 0:
+            ones = torch.ones((1, int(idx.sel.numel()), idx.Mloc), dtype=torch.bool, device=shard.device)
+            gt = QueryGT(1, Nq, idx.sel, idx.own_local, ones, idx.base, idx.all_local, idx.Mloc)
+        else:
+            gt = QueryGT(1, Nq)
+    elif own_global is not None and labels is not None:
+        gt = prepare_gt(shard, own_global, labels)
+    rd = ri = None
+    if gt is not None:
+        if gt.sel is not None:
+            mine = Qs if gt.all_local else [Q[gt.sel].contiguous() for Q in Qs]
+            sc = ops.score_fusion_own(mine, banks, fused.weights, gt.own_local)                  # [n_sel, Mown], +inf padded
+            keys = ops.gt_best_keys(sc, gt.labels, gt.base, gt.sel, Nq)
+        else:
+            keys = torch.full((gt.num_thresholds, Nq), KEY_INF, dtype=torch.int64, device=shard.device)
+        dist = _group(world)
+        if dist is not None:
+            dist.all_reduce(keys, op=dist.ReduceOp.MIN)
+        if level == "moments" and bool((keys == KEY_INF).any()):
+            raise_no_positive()
+        rd, ri = _unpack_key(keys)
+        rd, ri = rd.contiguous(), ri.contiguous()
+    od, oi, cnt = _exchange(*ops.score_fusion(Qs, banks, fused.weights, k, level, rd, ri, workspace=workspace), k, ops, world)
+    vid = _video_of(shard, oi) if k > 0 else None
+    if cnt is not None and level == "videos":
+        cnt = cnt[0]
+    return od, oi, vid, cnt
+
+
 def corpus_sentence_topk(shard: CorpusShard, S, probes, k, own_sentence=None, ops=None, world=1, workspace=None):
     """Sentence retrieval for moments over the corpus: per probe ``(global video, start_t, end_t)`` (inclusive clip span,
     ``utils.generate_moments`` units; host array-like [Nm, 3]) the k sentences of the bank ``S`` [Ns, D] with the smallest mean clip
@@ -1366,6 +1464,64 @@ class TorchCpuOps:
         sub = torch.stack([self._pad_k(r, longest) for r in rows]) if rows else torch.zeros((0, 0), dtype=torch.int64)
         kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nq), rank_idx.reshape(-1, Nq))
         return self._topk_lists(sub, k) + (self._counts_below(sub, kstar, count_lt),)
+
+    def _fusion_check(self, Qs, banks, weights, who):
+        """Late fusion on this provider: the streams' banks must describe the same videos -> (Qs, banks, fp32 weights)."""
+        Qs, banks = list(Qs), list(banks)
+        if len(Qs) != len(banks):
+            raise ValueError(f"{who}: {len(Qs)} query matrices for {len(banks)} banks")
+        w = fusion_weights(weights, len(banks))
+        for s, b in enumerate(banks[1:], 1):
+            if b.id_base != banks[0].id_base or not torch.equal(b.clip_off, banks[0].clip_off):
+                raise ValueError(f"{who}: bank {s} does not describe the videos of bank 0 (clip_off, id_base)")
+        return Qs, banks, w
+
+    def _fused_clip_dist(self, Qs, embs, w, eps=1e-6):
+        """[Nq, C] fused clip distances: f = w_0 d_0, f = f + w_s d_s -- SEPARATE float32 multiplies and adds on the provider's one
+        ``_clip_dist``, so the CPU device carries the fusion kernels' bits."""
+        f = None
+        for s, (Q, V) in enumerate(zip(Qs, embs)):
+            t = np.multiply(w[s], self._clip_dist(Q, V, eps).numpy(), dtype=np.float32)
+            f = t if f is None else np.add(f, t, dtype=np.float32)
+        return torch.from_numpy(f)
+
+    def score_fusion_own(self, Qs, banks, weights, own_local, eps=1e-6):
+        """Fused scores of each query against its own video: the layout of ``score_own`` (same semantics as
+        ``_vfr.score_fusion_own``)."""
+        Qs, banks, w = self._fusion_check(Qs, banks, weights, "score_fusion_own")
+        counts = banks[0].counts
+        nmax = max(counts) if counts else 0
+        Nq = Qs[0].shape[0]
+        out = torch.full((Nq, nmax * (nmax + 1) // 2), float("inf"))
+        off = banks[0].clip_off.tolist()
+        for q, v in enumerate(own_local.tolist()):
+            if not 0 <= v < len(counts):
+                continue
+            f = self._fused_clip_dist([Q[q:q + 1] for Q in Qs], [b.emb[off[v]:off[v + 1]] for b in banks], w, eps)
+            sc = self._video_scores(f)[0]
+            out[q, :sc.numel()] = sc
+        return out
+
+    def score_fusion(self, Qs, banks, weights, k, level="moments", rank_dist=None, rank_idx=None, count_lt=None, workspace=None,
+                     eps=1e-6):
+        """Late-fusion retrieval from dense scores (same semantics as ``_vfr.score_fusion``): the fused clip distances, the moment
+        chain on them (``_video_scores``), keys (score, global id); moments, or each video's smallest key."""
+        if level not in ("moments", "videos"):
+            raise ValueError(f"score_fusion: unknown level {level!r} (moments, videos)")
+        Qs, banks, w = self._fusion_check(Qs, banks, weights, "score_fusion")
+        b0 = banks[0]
+        Nq = Qs[0].shape[0]
+        f = self._fused_clip_dist(Qs, [b.emb for b in banks], w, eps)
+        off = b0.clip_off.tolist()
+        cols = [self._video_scores(f[:, off[v]:off[v + 1]]) for v in range(len(off) - 1)]
+        sc = torch.cat(cols, dim=1) if cols else torch.zeros((Nq, 0))
+        keys = _pack_key(sc, (b0.id_base + torch.arange(sc.shape[1]))[None, :].expand_as(sc))
+        if level == "videos":
+            mo = csr_offsets(b0.counts)[1]
+            best = [keys[:, int(a):int(b)].min(dim=1).values for a, b in zip(mo[:-1], mo[1:]) if b > a]
+            keys = torch.stack(best, dim=1) if best else torch.zeros((Nq, 0), dtype=torch.int64)
+        kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nq), rank_idx.reshape(-1, Nq))
+        return self._topk_lists(keys, k) + (self._counts_below(keys, kstar, count_lt),)
 
     def score_sentences(self, S, bank, probes, k, vid_base=0, sent_base=0, rank_dist=None, rank_idx=None, count_lt=None, bad=None,
                         workspace=None, eps=1e-6):

@@ -388,3 +388,55 @@ def evaluate_paragraphs(model, video_iterator, lang_iterator, annotations, devic
     if return_topk:
         return out, (score, vid, videos)
     return out
+
+
+def evaluate_fusion(models, video_iterators, lang_iterators, annotations, device, weights, level="moments", atk=(1, 10, 100),
+                    thresholds=(0.5, 0.7), rank=0, world=1, return_topk=0):
+    """Late-fusion retrieval metrics: one ``(model, video iterator, language iterator)`` per stream -- a VGG and a ResNet model, RGB
+    and flow, several seeds; the language iterators differ because the vocabularies may -- and one weight per stream (finite,
+    >= 0, at most 4 streams).  Every moment is ranked by the weighted sum of the streams' clip distances carried through the moment
+    chain (``engine.corpus_fusion_topk``; DESIGN section 4 states the arithmetic).
+
+    ``level`` "moments": per IoU threshold the 0-based rank of the best ground-truth-positive moment in the fused order ->
+    ``{"model, IoU=<thr>": {"R@1", "R@10", "R@100", "MR"}}`` as ``evaluate`` (strict labels; a query without a positive moment
+    raises IndexError); "videos": the 0-based rank of the own video's best fused key among the videos' -> ``{"video": {...}}`` as
+    ``evaluate_videos``.  One stream with weight 1, or weights (1, 0, ..), give exactly ``evaluate`` / ``evaluate_videos`` of
+    stream 0.  The streams must iterate the same videos with the same clip counts and the same queries in the same order:
+    ValueError otherwise, as for a bad weight.  ``return_topk`` = k also returns ``(dist, moment idx, video idx)`` [Nq, k]."""
+    models, video_iterators, lang_iterators = list(models), list(video_iterators), list(lang_iterators)
+    if level not in ("moments", "videos"):
+        raise ValueError(f"evaluate_fusion: unknown level {level!r} (moments, videos)")
+    if not (len(models) == len(video_iterators) == len(lang_iterators)):
+        raise ValueError(f"evaluate_fusion: {len(models)} models, {len(video_iterators)} video and {len(lang_iterators)} language iterators")
+    w = engine.fusion_weights(weights, len(models))
+    shards, names_all, Qs, first = [], [], [], None
+    for s, (model, vi, li) in enumerate(zip(models, video_iterators, lang_iterators)):
+        with _eval_mode(model):
+            ops, _, annot_ids, shard, names, Q, own = _prepare(model, vi, li, device, rank, world)
+        if first is None:
+            first = (annot_ids, own)
+        elif list(annot_ids) != list(first[0]) or (own is None) != (first[1] is None) or (own is not None and not np.array_equal(own, first[1])):
+            raise ValueError(f"evaluate_fusion: stream {s} iterates other queries (or another query order) than stream 0")
+        shards.append(shard)
+        names_all.append(names)
+        Qs.append(Q)
+    annot_ids, own = first
+    if shards[0] is None:
+        empty = ({"video": get_metrics(_empty_metrics(atk))} if level == "videos" else
+                 {f"model, IoU={thr}": get_metrics(_empty_metrics(atk)) for thr in thresholds})
+        return (empty, (None, None, None)) if return_topk else empty
+    fused = engine.fuse_corpora(shards, w, names=names_all)
+    shard = fused.first
+    K = int(return_topk)
+    if level == "videos":
+        dist, idx, vid, ranks = engine.corpus_fusion_topk(fused, Qs, K, "videos", own_global=own, ops=ops, world=world)
+        out = {"video": get_metrics(_rank_metrics(ranks.cpu().numpy(), atk))}
+    else:
+        times = [annotations[a]["times"] for a in annot_ids]
+        labels = engine.gt_labels(times, shard.counts_all[own], list(thresholds), True, shard.device, ops)
+        dist, idx, vid, ranks = engine.corpus_fusion_topk(fused, Qs, K, "moments", own_global=own, labels=labels, ops=ops, world=world)
+        ranks = ranks.cpu().numpy()
+        out = {f"model, IoU={thr}": get_metrics(_rank_metrics(ranks[r], atk)) for r, thr in enumerate(thresholds)}
+    if return_topk:
+        return out, (dist, idx, vid)
+    return out
