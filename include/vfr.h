@@ -422,6 +422,32 @@ int vfr_score_fusion_f32(const float *const *Q_host, const float *const *V_host,
                          int min_clips, int max_clips, float eps, int64_t id_base, int level, int k, float *out_dist,
                          int64_t *out_idx, int num_rank, const float *rank_dist, const int64_t *rank_idx, int64_t *count_lt,
                          void *workspace, size_t workspace_bytes, vfr_stream_t stream);
+/* ---- fusion weight sweep: the two calls above for a GRID of W weight vectors (w_host [W][S] row-major, host, every weight finite
+ * and >= 0; 1 <= W <= VFR_FUSION_MAX_SWEEP) over the same streams in one pass -- what tuning the weights on a validation split
+ * needs.  The stream clip distances d_s[q, c] do not depend on the weights: they are computed once, and per weight vector only the
+ * fuse and the moment chain are repeated.  For every row w of the grid, BIT FOR BIT:
+ *   vfr_score_fusion_sweep_own_f32: scores[w] [Nq, Mmax] = what vfr_score_fusion_own_f32 writes at w (scores is [W, Nq, Mmax]).
+ *   vfr_score_fusion_sweep_f32:     count_lt[w] [num_rank, Nq] += what vfr_score_fusion_f32 adds at w with k = 0 and the rank keys
+ *                                   rank_dist[w] / rank_idx[w] (all three [W, num_rank, Nq]).  Counts only: no lists, no workspace.
+ * Stream arrays, level, num_rank <= 4, max_clips <= 64, id_base and the ADDED counts (shards chain) are as in the single-weight
+ * calls; the grid travels by value in the kernel arguments; nothing waits for the host.  Nq = 0, Nv = 0 or num_rank = 0: VFR_OK,
+ * nothing written (sweep_own still fills +inf when Nq > 0).
+ * LDS of a vfr_score_fusion_sweep_f32 wave, in bytes, rows = max(max_clips, 1):
+ *     4 * (sum over s of round_up(D_s, 4))       the query rows
+ *   + 4 * 64 * rows * S                          the per-stream clip distances of a block of 64 videos
+ *   + 4 * 64 * rows                              the fused clip distances of the current weight vector
+ *   + 16 * W * num_rank                          the rank keys and the wave's 64-bit counts
+ * must not exceed 65536: VFR_EUNSUPPORTED (the message states the bytes) otherwise -- S = 4 at max_clips = 64 never fits, S = 2 at
+ * max_clips = 64 does for query rows of up to 3 840 floats in all.  VFR_EINVAL before anything is enqueued for W outside 1 .. 16, a null
+ * array, a bad weight anywhere in the grid (the message names the row) and the bad arguments of the single-weight calls.      */
+#define VFR_FUSION_MAX_SWEEP 16
+int vfr_score_fusion_sweep_own_f32(const float *const *Q_host, const float *const *V_host, const int *D_host, const float *w_host, int W,
+                                   int S, int64_t Nq, const int32_t *clip_offsets, const int32_t *own, int Nv, int max_clips, float eps,
+                                   int Mmax, float *scores, vfr_stream_t stream);
+int vfr_score_fusion_sweep_f32(const float *const *Q_host, const float *const *V_host, const int *D_host, const float *w_host, int W,
+                               int S, int64_t Nq, const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv, int total_clips,
+                               int max_clips, float eps, int64_t id_base, int level, int num_rank, const float *rank_dist,
+                               const int64_t *rank_idx, int64_t *count_lt, vfr_stream_t stream);
 /* Device self-check of the arithmetic model the pre-filter's margins and the MFMA GEMMs' bit-exactness assume: a
  * v_mfma_f32_16x16x4_f32 = four fp32 fmas, k ascending, on its accumulator (denormals kept).  A, B [16, K] device rows
  * (K % 4 == 0; make them adversarial: wide exponent range, cancellation, denormals): C = A B^T by the matrix pipe against an

@@ -20,13 +20,13 @@ for line in out.splitlines():
     t = m.group(1).strip()
     if t.startswith("Function Name:"):
         name = subprocess.run(["c++filt", t.split(":", 1)[1].strip()], capture_output=True, text=True).stdout.strip()
-        cur = {"name": re.sub(r"\(.*", "", name)}
+        cur = {"name": re.sub(r"\((?!anonymous namespace\)).*", "", name).replace("(anonymous namespace)::", "")}
         rows.append(cur)
     elif cur is not None and ":" in t:
         k, v = t.split(":", 1)
         cur[k.strip()] = v.strip()
-print(f"{'kernel':70s} VGPR AGPR  SGPR scratch occ  vspill")
+print(f"{'kernel':70s} VGPR AGPR  SGPR scratch occ  vspill static-LDS")
 for r in rows:
     if flt in r["name"]:
-        print(f"{r['name'][:70]:70s} {r.get('VGPRs','?'):>4} {r.get('AGPRs','?'):>4} {r.get('SGPRs','?'):>5} {r.get('ScratchSize [bytes/lane]','?'):>7} "
-              f"{r.get('Occupancy [waves/SIMD]','?'):>3} {r.get('VGPRs Spill','?'):>6}")
+        print(f"{r['name'][:70]:70s} {r.get('VGPRs','?'):>4} {r.get('AGPRs','?'):>4} {r.get('SGPRs', r.get('TotalSGPRs', '?')):>5} {r.get('ScratchSize [bytes/lane]','?'):>7} "
+              f"{r.get('Occupancy [waves/SIMD]','?'):>3} {r.get('VGPRs Spill','?'):>6} {r.get('LDS Size [bytes/block]','?'):>10}")

@@ -79,6 +79,9 @@ SIGNATURES = {
     "vfr_score_fusion_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "vfr_score_fusion_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _i32, _vp, _vp,
                                     _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vfr_score_fusion_sweep_own_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp]),
+    "vfr_score_fusion_sweep_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _f32, _i64, _i32, _i32,
+                                          _vp, _vp, _vp, _vp]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "vfr_topk_pack_keys": (_i32, [_vp, _vp, _i64, _vp, _vp]),
@@ -724,6 +727,87 @@ def score_fusion(Qs, banks, weights, k: int, level: str = "moments", rank_dist=N
                                       _ptr(rank_dist), _ptr(rank_idx), _ptr(count_lt), workspace.data_ptr(), nbytes, _stream()),
            "vfr_score_fusion_f32")
     return od, oi, count_lt
+
+
+FUSION_MAX_SWEEP = 16                         # include/vfr.h VFR_FUSION_MAX_SWEEP
+
+
+def fusion_weight_grid(grid, S: int) -> np.ndarray:
+    """A grid of stream weights as fp32 [W, S], W >= 1: every row as ``fusion_weights`` takes it (ValueError otherwise).  Host only."""
+    if not 1 <= S <= FUSION_MAX_STREAMS:
+        raise ValueError(f"late fusion takes 1 .. {FUSION_MAX_STREAMS} streams, got {S}")
+    g = np.asarray(grid.cpu() if isinstance(grid, torch.Tensor) else grid, dtype=np.float64)
+    if g.ndim != 2 or g.shape[0] < 1 or g.shape[1] != S:
+        raise ValueError(f"late fusion: a weight grid is [W >= 1, {S}], got shape {g.shape}")
+    g32 = np.ascontiguousarray(g, dtype=np.float32)
+    bad = np.nonzero(~(np.isfinite(g32) & (g32 >= 0)).all(axis=1))[0]
+    if len(bad):
+        raise ValueError(f"late fusion: weights must be finite and >= 0, got {g[bad[0]].tolist()} in grid row {int(bad[0])}")
+    return g32
+
+
+def _sweep_hosts(hosts, g: np.ndarray):
+    """The host arrays of ``_fusion_streams`` with the weights replaced by the rows ``g`` [W <= 16, S] of a grid."""
+    Qh, Vh, Dh, _, S = hosts
+    return Qh, Vh, Dh, (ctypes.c_float * g.size)(*g.reshape(-1).tolist()), g.shape[0], S
+
+
+def score_fusion_sweep_own(Qs, banks, grid, own: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+    """``score_fusion_own`` for every row of a weight grid [W, S] in one pass (include/vfr.h vfr_score_fusion_sweep_own_f32):
+    [W, Nq, Mmax], slice w bit for bit ``score_fusion_own(Qs, banks, grid[w], own)``.  The stream clip distances are computed once
+    per 16 rows of the grid (a longer grid is split into slices of 16)."""
+    g = fusion_weight_grid(grid, len(list(banks)))
+    Qs, banks, hosts = _fusion_streams(Qs, banks, g[0], "score_fusion_sweep_own")
+    b0 = banks[0]
+    own = _dev(own, torch.int32, "own")
+    Nq = Qs[0].shape[0]
+    if own.numel() != Nq:
+        raise ValueError(f"score_fusion_sweep_own: {own.numel()} own videos for {Nq} queries")
+    Mmax = b0.max_clips * (b0.max_clips + 1) // 2
+    out = torch.empty((len(g), Nq, Mmax), dtype=torch.float32, device=Qs[0].device)
+    for a in range(0, len(g), FUSION_MAX_SWEEP):
+        part = out[a:a + FUSION_MAX_SWEEP]
+        _check(lib().vfr_score_fusion_sweep_own_f32(*_sweep_hosts(hosts, g[a:a + FUSION_MAX_SWEEP]), Nq, b0.clip_off.data_ptr(),
+                                                    _ptr(own) if Nq else 0, b0.num_videos, b0.max_clips, eps, Mmax,
+                                                    part.data_ptr() if part.numel() else 0, _stream()),
+               "vfr_score_fusion_sweep_own_f32")
+    return out
+
+
+def score_fusion_sweep(Qs, banks, grid, level: str, rank_dist, rank_idx, count_lt=None, eps: float = 1e-6) -> torch.Tensor:
+    """Rank counts of late fusion for every row of a weight grid [W, S] in one pass (include/vfr.h vfr_score_fusion_sweep_f32).
+    rank_dist / rank_idx [W, R, Nq] (or [W, Nq]), R <= 4: the rank keys of each weight vector; ``count_lt`` [W, R, Nq] int64 += the
+    moments (``level`` "moments") or videos ("videos") that sort strictly before each key (allocated zeroed when None) -- slice w
+    bit for bit what ``score_fusion(Qs, banks, grid[w], 0, level, rank_dist[w], rank_idx[w])`` counts.  No lists and no workspace;
+    a grid of more than 16 rows is split into slices of 16.  Returns count_lt."""
+    if level not in FUSION_LEVELS:
+        raise ValueError(f"score_fusion_sweep: unknown level {level!r} (moments, videos)")
+    g = fusion_weight_grid(grid, len(list(banks)))
+    Qs, banks, hosts = _fusion_streams(Qs, banks, g[0], "score_fusion_sweep")
+    b0 = banks[0]
+    Nq, dev, W = Qs[0].shape[0], Qs[0].device, len(g)
+    if rank_dist is None or rank_idx is None:
+        raise ValueError("score_fusion_sweep: rank_dist and rank_idx [W, R, Nq] are required (the sweep only counts)")
+    rank_dist, rank_idx = _dev(rank_dist, torch.float32, "rank_dist"), _dev(rank_idx, torch.int64, "rank_idx")
+    if rank_dist.dim() == 2 and rank_idx.dim() == 2:
+        rank_dist, rank_idx = rank_dist[:, None], rank_idx[:, None]
+    if rank_dist.dim() != 3 or rank_dist.shape[0] != W or rank_dist.shape[2] != Nq or rank_idx.shape != rank_dist.shape:
+        raise ValueError(f"score_fusion_sweep: rank_dist / rank_idx must be [{W}, R, {Nq}], got {tuple(rank_dist.shape)} / "
+                         f"{tuple(rank_idx.shape)}")
+    R = rank_dist.shape[1]
+    if count_lt is None:
+        count_lt = torch.zeros((W, R, Nq), dtype=torch.int64, device=dev)
+    count_lt = _dev(count_lt, torch.int64, "count_lt")
+    if count_lt.shape != rank_dist.shape:
+        raise ValueError(f"score_fusion_sweep: count_lt {tuple(count_lt.shape)} for rank keys {tuple(rank_dist.shape)}")
+    for a in range(0, W, FUSION_MAX_SWEEP):
+        z = a + FUSION_MAX_SWEEP
+        _check(lib().vfr_score_fusion_sweep_f32(*_sweep_hosts(hosts, g[a:z]), Nq, b0.clip_off.data_ptr(), b0.mom_off.data_ptr(),
+                                                b0.num_videos, b0.total_clips, b0.max_clips, eps, b0.id_base, FUSION_LEVELS[level],
+                                                R if Nq else 0,             # (no queries: the empty tensors have no address)
+                                                _ptr(rank_dist[a:z]), _ptr(rank_idx[a:z]), _ptr(count_lt[a:z]), _stream()),
+               "vfr_score_fusion_sweep_f32")
+    return count_lt
 
 
 def score_sentences(S: torch.Tensor, bank: VideoBank, probes: torch.Tensor, k: int, vid_base: int = 0, sent_base: int = 0,

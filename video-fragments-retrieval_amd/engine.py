@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ._vfr import KEY_EMPTY as KEY_INF, csr_offsets, fusion_weights   # (does not load libvfr.so)  KEY_INF = key of (+inf, max id): "no positive moment here"
+from ._vfr import KEY_EMPTY as KEY_INF, csr_offsets, fusion_weight_grid, fusion_weights   # (does not load libvfr.so)  KEY_INF = key of (+inf, max id): "no positive moment here"
 from .utils import generate_moments, get_iou
 
 
@@ -91,6 +91,12 @@ class HipOps:
 
     def score_fusion_own(self, Qs, banks, weights, own_local):
         return self.v.score_fusion_own(Qs, banks, weights, own_local)
+
+    def score_fusion_sweep_own(self, Qs, banks, grid, own_local):
+        return self.v.score_fusion_sweep_own(Qs, banks, grid, own_local)
+
+    def score_fusion_sweep(self, Qs, banks, grid, level, rank_dist, rank_idx, count_lt=None):
+        return self.v.score_fusion_sweep(Qs, banks, grid, level, rank_dist, rank_idx, count_lt=count_lt)
 
     def slice_bank(self, bank, counts, v0, v1):
         return self.v.slice_bank(bank, counts, v0, v1)
@@ -923,6 +929,66 @@ def corpus_fusion_topk(fused: FusedCorpus, Qs, k, level="moments", own_global=No
     return od, oi, vid, cnt
 
 
+def simplex_grid(S, steps):
+    """Every weight vector of ``S`` components ``i / steps`` (integers i >= 0) that sum to 1, in lexicographic order: float32
+    [C(steps + S - 1, S - 1), S] -- the usual grid for tuning fusion weights; ``simplex_grid(2, 10)`` is (0, 1), (0.1, 0.9), ..,
+    (1, 0)."""
+    S, steps = int(S), int(steps)
+    if S < 1 or steps < 1:
+        raise ValueError(f"simplex_grid: S = {S} components in {steps} steps (both >= 1)")
+
+    def rows(left, total):
+        if left == 1:
+            return [(total,)]
+        return [(i,) + r for i in range(total + 1) for r in rows(left - 1, total - i)]
+    return (np.asarray(rows(S, steps), np.float64) / steps).astype(np.float32)
+
+
+def corpus_fusion_sweep(fused: FusedCorpus, Qs, grid, level="moments", own_global=None, labels=None, ops=None, world=1):
+    """The ranks of ``corpus_fusion_topk`` for every row of a weight grid [W, S] (``simplex_grid``) in one pass over the corpus --
+    what tuning the weights needs; ``fused.weights`` is not used.  The stream clip distances are computed once per 16 rows of the
+    grid, the fuse and the moment chain per row.  Ground truth as ``corpus_fusion_topk`` takes it: "moments" with ``own_global``
+    and ``labels`` [R, Nq, Mmax] -> ranks [W, R, Nq] int64 (IndexError when, for some row of the grid, a query has no positive
+    moment); "videos" with ``own_global`` -> ranks [W, Nq].  Slice w equals the ranks ``corpus_fusion_topk`` returns with the weights
+    ``grid[w]``.  Sharded: the keys [W, R, Nq] go through ONE all-reduce (MIN), the counts through one (SUM)."""
+    ops = ops or HipOps()
+    if level not in ("moments", "videos"):
+        raise ValueError(f"corpus_fusion_sweep: unknown level {level!r} (moments, videos)")
+    Qs = list(Qs)
+    if len(Qs) != len(fused.shards):
+        raise ValueError(f"corpus_fusion_sweep: {len(Qs)} query matrices for {len(fused.shards)} streams")
+    grid = fusion_weight_grid(grid, len(fused.shards))
+    shard, banks = fused.first, fused.banks
+    Nq, W = Qs[0].shape[0], len(grid)
+    if own_global is None or (level == "moments" and labels is None):
+        raise ValueError("corpus_fusion_sweep: ranks need own_global (and labels at the moment level)")
+    if level == "videos":
+        idx = gt_index(shard, own_global)
+        if idx.sel is not None and idx.Mloc > 0:
+            ones = torch.ones((1, int(idx.sel.numel()), idx.Mloc), dtype=torch.bool, device=shard.device)
+            gt = QueryGT(1, Nq, idx.sel, idx.own_local, ones, idx.base, idx.all_local, idx.Mloc)
+        else:
+            gt = QueryGT(1, Nq)
+    else:
+        gt = prepare_gt(shard, own_global, labels)
+    if gt.sel is not None:
+        mine = Qs if gt.all_local else [Q[gt.sel].contiguous() for Q in Qs]
+        sc = ops.score_fusion_sweep_own(mine, banks, grid, gt.own_local)                         # [W, n_sel, Mown], +inf padded
+        keys = torch.stack([ops.gt_best_keys(sc[w], gt.labels, gt.base, gt.sel, Nq) for w in range(W)])
+    else:
+        keys = torch.full((W, gt.num_thresholds, Nq), KEY_INF, dtype=torch.int64, device=shard.device)
+    dist = _group(world)
+    if dist is not None:
+        dist.all_reduce(keys, op=dist.ReduceOp.MIN)
+    if level == "moments" and bool((keys == KEY_INF).any()):
+        raise_no_positive()
+    rd, ri = _unpack_key(keys)
+    cnt = ops.score_fusion_sweep(Qs, banks, grid, level, rd.contiguous(), ri.contiguous())
+    if dist is not None:
+        dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+    return cnt[:, 0] if level == "videos" else cnt
+
+
 def corpus_sentence_topk(shard: CorpusShard, S, probes, k, own_sentence=None, ops=None, world=1, workspace=None):
     """Sentence retrieval for moments over the corpus: per probe ``(global video, start_t, end_t)`` (inclusive clip span,
     ``utils.generate_moments`` units; host array-like [Nm, 3]) the k sentences of the bank ``S`` [Ns, D] with the smallest mean clip
@@ -1522,6 +1588,27 @@ class TorchCpuOps:
             keys = torch.stack(best, dim=1) if best else torch.zeros((Nq, 0), dtype=torch.int64)
         kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nq), rank_idx.reshape(-1, Nq))
         return self._topk_lists(keys, k) + (self._counts_below(keys, kstar, count_lt),)
+
+    def score_fusion_sweep_own(self, Qs, banks, grid, own_local, eps=1e-6):
+        """``score_fusion_own`` per row of the weight grid, [W, Nq, Mmax] (same semantics as ``_vfr.score_fusion_sweep_own``): the
+        provider's one ``_clip_dist`` and its fp32 multiply / add fuse, row by row."""
+        grid = fusion_weight_grid(grid, len(list(banks)))
+        return torch.stack([self.score_fusion_own(Qs, banks, w, own_local, eps) for w in grid])
+
+    def score_fusion_sweep(self, Qs, banks, grid, level, rank_dist, rank_idx, count_lt=None, eps=1e-6):
+        """The rank counts of ``score_fusion`` (k = 0) per row of the weight grid, [W, R, Nq] (same semantics as
+        ``_vfr.score_fusion_sweep``); ``count_lt`` [W, R, Nq] is added."""
+        grid = fusion_weight_grid(grid, len(list(banks)))
+        W, Nq = len(grid), Qs[0].shape[0]
+        if rank_dist is None or rank_idx is None:
+            raise ValueError("score_fusion_sweep: rank_dist and rank_idx [W, R, Nq] are required (the sweep only counts)")
+        if rank_dist.dim() == 2 and rank_idx.dim() == 2:
+            rank_dist, rank_idx = rank_dist[:, None], rank_idx[:, None]
+        if rank_dist.dim() != 3 or rank_dist.shape[0] != W or rank_dist.shape[2] != Nq or rank_idx.shape != rank_dist.shape:
+            raise ValueError(f"score_fusion_sweep: rank_dist / rank_idx must be [{W}, R, {Nq}], got {tuple(rank_dist.shape)} / "
+                             f"{tuple(rank_idx.shape)}")
+        return torch.stack([self.score_fusion(Qs, banks, grid[w], 0, level, rank_dist[w], rank_idx[w],
+                                              None if count_lt is None else count_lt[w], eps=eps)[2] for w in range(W)])
 
     def score_sentences(self, S, bank, probes, k, vid_base=0, sent_base=0, rank_dist=None, rank_idx=None, count_lt=None, bad=None,
                         workspace=None, eps=1e-6):

@@ -390,6 +390,31 @@ def evaluate_paragraphs(model, video_iterator, lang_iterator, annotations, devic
     return out
 
 
+def _fusion_streams(models, video_iterators, lang_iterators, device, rank, world, who):
+    """The streams of a late fusion, encoded: one ``_prepare`` per (model, video iterator, language iterator); every stream must
+    iterate the queries of stream 0 in its order (ValueError).  Returns (ops, annot_ids, own, shards, names per stream, Qs);
+    ``shards[0] is None`` for an empty corpus."""
+    shards, names_all, Qs, first = [], [], [], None
+    for s, (model, vi, li) in enumerate(zip(models, video_iterators, lang_iterators)):
+        with _eval_mode(model):
+            ops, _, annot_ids, shard, names, Q, own = _prepare(model, vi, li, device, rank, world)
+        if first is None:
+            first = (annot_ids, own)
+        elif list(annot_ids) != list(first[0]) or (own is None) != (first[1] is None) or (own is not None and not np.array_equal(own, first[1])):
+            raise ValueError(f"{who}: stream {s} iterates other queries (or another query order) than stream 0")
+        shards.append(shard)
+        names_all.append(names)
+        Qs.append(Q)
+    annot_ids, own = first
+    return ops, annot_ids, own, shards, names_all, Qs
+
+
+def _fusion_empty(level, atk, thresholds):
+    """The metric dict of a fusion over an empty corpus."""
+    return ({"video": get_metrics(_empty_metrics(atk))} if level == "videos" else
+            {f"model, IoU={thr}": get_metrics(_empty_metrics(atk)) for thr in thresholds})
+
+
 def evaluate_fusion(models, video_iterators, lang_iterators, annotations, device, weights, level="moments", atk=(1, 10, 100),
                     thresholds=(0.5, 0.7), rank=0, world=1, return_topk=0):
     """Late-fusion retrieval metrics: one ``(model, video iterator, language iterator)`` per stream -- a VGG and a ResNet model, RGB
@@ -409,21 +434,10 @@ def evaluate_fusion(models, video_iterators, lang_iterators, annotations, device
     if not (len(models) == len(video_iterators) == len(lang_iterators)):
         raise ValueError(f"evaluate_fusion: {len(models)} models, {len(video_iterators)} video and {len(lang_iterators)} language iterators")
     w = engine.fusion_weights(weights, len(models))
-    shards, names_all, Qs, first = [], [], [], None
-    for s, (model, vi, li) in enumerate(zip(models, video_iterators, lang_iterators)):
-        with _eval_mode(model):
-            ops, _, annot_ids, shard, names, Q, own = _prepare(model, vi, li, device, rank, world)
-        if first is None:
-            first = (annot_ids, own)
-        elif list(annot_ids) != list(first[0]) or (own is None) != (first[1] is None) or (own is not None and not np.array_equal(own, first[1])):
-            raise ValueError(f"evaluate_fusion: stream {s} iterates other queries (or another query order) than stream 0")
-        shards.append(shard)
-        names_all.append(names)
-        Qs.append(Q)
-    annot_ids, own = first
+    ops, annot_ids, own, shards, names_all, Qs = _fusion_streams(models, video_iterators, lang_iterators, device, rank, world,
+                                                                 "evaluate_fusion")
     if shards[0] is None:
-        empty = ({"video": get_metrics(_empty_metrics(atk))} if level == "videos" else
-                 {f"model, IoU={thr}": get_metrics(_empty_metrics(atk)) for thr in thresholds})
+        empty = _fusion_empty(level, atk, thresholds)
         return (empty, (None, None, None)) if return_topk else empty
     fused = engine.fuse_corpora(shards, w, names=names_all)
     shard = fused.first
@@ -440,3 +454,43 @@ def evaluate_fusion(models, video_iterators, lang_iterators, annotations, device
     if return_topk:
         return out, (dist, idx, vid)
     return out
+
+
+def sweep_fusion(models, video_iterators, lang_iterators, annotations, device, grid, level="moments", atk=(1, 10, 100),
+                 thresholds=(0.5, 0.7), rank=0, world=1, select=None):
+    """``evaluate_fusion`` for every row of a weight grid [W, S] (``engine.simplex_grid``) with ONE encoding of the streams and one
+    pass over the corpus per 16 rows (``engine.corpus_fusion_sweep``): tuning the fusion weights on a validation split.
+
+    Returns ``(metrics, best)``: ``metrics[i]`` is exactly the dict ``evaluate_fusion`` returns with ``weights = grid[i]``;
+    ``best`` is the index of the row chosen by ``select = (dict key, metric name)``, e.g. ``("model, IoU=0.5", "R@1")`` or
+    ``("video", "MR")`` -- "MR" is minimised, every other metric maximised, a tie goes to the lowest index -- and None without
+    ``select``.  Streams, levels and errors are those of ``evaluate_fusion``; a bad row of the grid raises ValueError."""
+    models, video_iterators, lang_iterators = list(models), list(video_iterators), list(lang_iterators)
+    if level not in ("moments", "videos"):
+        raise ValueError(f"sweep_fusion: unknown level {level!r} (moments, videos)")
+    if not (len(models) == len(video_iterators) == len(lang_iterators)):
+        raise ValueError(f"sweep_fusion: {len(models)} models, {len(video_iterators)} video and {len(lang_iterators)} language iterators")
+    grid = engine.fusion_weight_grid(grid, len(models))
+    ops, annot_ids, own, shards, names_all, Qs = _fusion_streams(models, video_iterators, lang_iterators, device, rank, world,
+                                                                 "sweep_fusion")
+    if shards[0] is None:
+        metrics = [_fusion_empty(level, atk, thresholds) for _ in grid]
+    else:
+        fused = engine.fuse_corpora(shards, grid[0], names=names_all)
+        shard = fused.first
+        if level == "videos":
+            ranks = engine.corpus_fusion_sweep(fused, Qs, grid, "videos", own_global=own, ops=ops, world=world).cpu().numpy()
+            metrics = [{"video": get_metrics(_rank_metrics(ranks[w], atk))} for w in range(len(grid))]
+        else:
+            times = [annotations[a]["times"] for a in annot_ids]
+            labels = engine.gt_labels(times, shard.counts_all[own], list(thresholds), True, shard.device, ops)
+            ranks = engine.corpus_fusion_sweep(fused, Qs, grid, "moments", own_global=own, labels=labels, ops=ops, world=world)
+            ranks = ranks.cpu().numpy()
+            metrics = [{f"model, IoU={thr}": get_metrics(_rank_metrics(ranks[w, r], atk)) for r, thr in enumerate(thresholds)}
+                       for w in range(len(grid))]
+    best = None
+    if select is not None:
+        key, name = select
+        vals = [m[key][name] for m in metrics]
+        best = int(np.argmin(vals) if name == "MR" else np.argmax(vals))          # argmin / argmax: the first of equal values
+    return metrics, best
