@@ -448,6 +448,50 @@ int vfr_score_fusion_sweep_f32(const float *const *Q_host, const float *const *V
                                int S, int64_t Nq, const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv, int total_clips,
                                int max_clips, float eps, int64_t id_base, int level, int num_rank, const float *rank_dist,
                                const int64_t *rank_idx, int64_t *count_lt, vfr_stream_t stream);
+/* ---- prior-aware retrieval: a MOMENT TABLE gives every moment position an additive bias or excludes it -- a temporal prior
+ * ("prior + model": how often training annotators chose a span), a proposal set (sliding windows of given lengths and stride), a
+ * length limit ("at most 3 clips").  The first variant that changes the moment score inside a video.
+ *   moment table  for every clip count n in 0 .. max_clips and every local moment j in utils.generate_moments(n) order one fp32
+ *           entry: table_off int32 [max_clips + 2] = prefix sums of n (n + 1) / 2 (table_off[n] = where the row of n-clip videos
+ *           starts, table_off[max_clips + 1] = all entries, at most 45 760 at 64 clips), table fp32 [table_off[max_clips + 1]].
+ *           Both are device arrays, the same on every shard.  An entry is a finite bias >= 0 or +inf = excluded.
+ *   biased score  g(q, v, j) = fl(score(q, v, j) + T[n_v][j]): score is the canonical chain, BIT-IDENTICAL to what
+ *           vfr_score_moments_f32 writes; then ONE rounded fp32 addition, contracted with nothing.  A moment is a candidate iff
+ *           g < +inf.
+ *   keys    (fp32 bits of g << 32) | (id_base + moment_offsets[v] + j) ascending, padding (+inf, -1), as vfr_score_topk_f32.
+ *           (Negative biases are not allowed: they would break the unsigned key order.)
+ *   bad     (nullable, device int) is set to 1 when an entry that was read is NaN or < 0, or a table_off entry that was read points
+ *           outside the table; such a moment (video) is treated as excluded.  Nothing is read or written out of bounds.
+ * A table of zeros gives vfr_score_topk_f32 / vfr_score_video_topk_f32 (VFR_SCORE_EXACT) BIT FOR BIT: distances are >= 0 and
+ * fl(x + 0) = x.
+ * vfr_score_prior_own_f32: each query against ONE video own[q] (local index; outside [0, Nv): the row is all +inf): biased scores
+ *   [Nq, Mmax], +inf at excluded moments and in the tail -- layout and meaning of vfr_score_own_f32, so the rows feed
+ *   vfr_gt_best_keys_f32 / vfr_gt_rank_keys_f32 unchanged.
+ * vfr_score_prior_f32: level VFR_PRIOR_MOMENTS: out_dist / out_idx [Nq,k] = the k smallest CANDIDATE keys; count_lt[r][q] += the
+ *   candidates that sort strictly before (rank_dist[r][q], rank_idx[r][q]).  VFR_PRIOR_VIDEOS: the k smallest best candidate keys
+ *   of the videos as (best g, id of that moment); a video without a candidate is never ranked or counted; count_lt[r][q] += the
+ *   videos whose best key sorts before the rank key.  num_rank <= 4, counts are ADDED (shards chain; lists merge with
+ *   vfr_topk_merge_f32); k = 0 with counts only is allowed.  The rank key (+inf, -1) counts every candidate (every video with one).
+ *   Nq = 0: nothing is written.  Nv = 0: the lists are padding, the counts stay.  min_clips is accepted for the shared argument
+ *   list and unused.
+ * Limits: max_clips <= 64, k <= 448, id_base + total moments < 2^32, Nq * k < 2^31, any D (D = 100 with 16-byte aligned Q and V
+ * takes the register-resident fast path).  VFR_EINVAL before anything is enqueued for the bad host-side arguments.  Exact arithmetic
+ * only (an MFMA bounds pre-filter would be sound -- a bias >= 0 keeps lower bounds valid -- and is not built).
+ * LDS of a vfr_score_prior_f32 wave, in bytes: 416 (the query row; fast path only) + 256 max(max_clips, 1) (the clip distances of a
+ * block of 64 videos) + 8 slots(k) (the key list: 128 / 256 / 512 slots for k <= 64 / 192 / 448): at most 20 896 at max_clips = 64.
+ * vfr_score_prior_workspace_bytes = 256 + 8 k Nq C, C = min(ceil(4096 / Nq), ceil(Nv / 64), 256) >= 1 = the bound on the chunks the
+ * video axis is cut into: O(Nq k), no Nq x Nv term (0 for a bad argument).                                                   */
+#define VFR_PRIOR_MOMENTS 0
+#define VFR_PRIOR_VIDEOS 1
+int vfr_score_prior_own_f32(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, const int32_t *own, int Nv,
+                            int max_clips, int D, float eps, int Mmax, const int32_t *table_off, const float *table, float *scores,
+                            int *bad, vfr_stream_t stream);
+size_t vfr_score_prior_workspace_bytes(int64_t Nq, int Nv, int k);
+int vfr_score_prior_f32(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv,
+                        int total_clips, int min_clips, int max_clips, int D, float eps, int64_t id_base, int level, int k,
+                        float *out_dist, int64_t *out_idx, int num_rank, const float *rank_dist, const int64_t *rank_idx,
+                        int64_t *count_lt, const int32_t *table_off, const float *table, int *bad, void *workspace,
+                        size_t workspace_bytes, vfr_stream_t stream);
 /* Device self-check of the arithmetic model the pre-filter's margins and the MFMA GEMMs' bit-exactness assume: a
  * v_mfma_f32_16x16x4_f32 = four fp32 fmas, k ascending, on its accumulator (denormals kept).  A, B [16, K] device rows
  * (K % 4 == 0; make them adversarial: wide exponent range, cancellation, denormals): C = A B^T by the matrix pipe against an

@@ -82,6 +82,10 @@ SIGNATURES = {
     "vfr_score_fusion_sweep_own_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp]),
     "vfr_score_fusion_sweep_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _f32, _i64, _i32, _i32,
                                           _vp, _vp, _vp, _vp]),
+    "vfr_score_prior_own_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "vfr_score_prior_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "vfr_score_prior_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _i32, _vp, _vp, _i32,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "vfr_topk_pack_keys": (_i32, [_vp, _vp, _i64, _vp, _vp]),
@@ -726,6 +730,77 @@ def score_fusion(Qs, banks, weights, k: int, level: str = "moments", rank_dist=N
                                       b0.min_clips, b0.max_clips, eps, b0.id_base, FUSION_LEVELS[level], k, _ptr(od), _ptr(oi), R,
                                       _ptr(rank_dist), _ptr(rank_idx), _ptr(count_lt), workspace.data_ptr(), nbytes, _stream()),
            "vfr_score_fusion_f32")
+    return od, oi, count_lt
+
+
+def table_offsets(max_clips: int) -> np.ndarray:
+    """int32 [max_clips + 2]: where the row of n-clip videos starts in a moment table (prefix sums of n (n + 1) / 2; the last entry is
+    the number of entries).  Host only."""
+    n = np.arange(max_clips + 1, dtype=np.int64)
+    return np.concatenate([[0], np.cumsum(n * (n + 1) // 2)]).astype(np.int32)
+
+
+def _prior_table(table, bank: VideoBank, device, who: str):
+    """The device arrays of a moment table (``engine.MomentTable``: ``max_clips``, ``table_off`` int32, ``table`` fp32), checked
+    against the bank.  A table built for longer videos serves a bank of shorter ones: its rows are a prefix."""
+    if table.max_clips < bank.max_clips:
+        raise ValueError(f"{who}: the moment table covers videos of up to {table.max_clips} clips, the bank has {bank.max_clips}")
+    off, val = _dev(table.table_off, torch.int32, "table_off"), _dev(table.table, torch.float32, "table")
+    if off.device != device or val.device != device:
+        raise ValueError(f"{who}: the moment table lives on {val.device}, the queries on {device}")
+    n = table.max_clips
+    if off.numel() != n + 2 or val.numel() != n * (n + 1) * (n + 2) // 6:
+        raise ValueError(f"{who}: a moment table of {n} clips has {n + 2} offsets and {n * (n + 1) * (n + 2) // 6} entries, got "
+                         f"{off.numel()} and {val.numel()}")
+    return off, val
+
+
+def score_prior_own(Q: torch.Tensor, bank: VideoBank, table, own: torch.Tensor, bad: torch.Tensor | None = None,
+                    eps: float = 1e-6) -> torch.Tensor:
+    """Biased scores of each query against ONE video ``own[q]`` (include/vfr.h vfr_score_prior_own_f32): [Nq, Mmax] =
+    fl(score + table entry) in ``utils.generate_moments`` order, +inf at excluded moments and in the tail -- the layout of
+    ``score_own``, so ``gt_best_keys`` / ``gt_rank_keys`` take it.  ``table``: an ``engine.MomentTable`` on the device; ``bad``
+    (int32 [1], optional) is set to 1 by an entry that is NaN or < 0."""
+    Q = _dev(Q, torch.float32, "Q")
+    own = _dev(own, torch.int32, "own")
+    Nq = Q.shape[0]
+    if Q.dim() != 2 or Q.shape[1] != bank.dim:
+        raise ValueError(f"score_prior_own: Q must be [Nq, {bank.dim}], got {tuple(Q.shape)}")
+    if own.numel() != Nq:
+        raise ValueError(f"score_prior_own: {own.numel()} own videos for {Nq} queries")
+    off, val = _prior_table(table, bank, Q.device, "score_prior_own")
+    Mmax = bank.max_clips * (bank.max_clips + 1) // 2
+    out = torch.empty((Nq, Mmax), dtype=torch.float32, device=Q.device)
+    _check(lib().vfr_score_prior_own_f32(Q.data_ptr(), Nq, bank.emb.data_ptr(), bank.clip_off.data_ptr(), _ptr(own) if Nq else 0,
+                                         bank.num_videos, bank.max_clips, bank.dim, eps, Mmax, off.data_ptr(), val.data_ptr(),
+                                         out.data_ptr() if out.numel() else 0, _ptr(bad), _stream()), "vfr_score_prior_own_f32")
+    return out
+
+
+def score_prior(Q: torch.Tensor, bank: VideoBank, table, k: int, level: str = "moments", rank_dist=None, rank_idx=None, count_lt=None,
+                workspace: torch.Tensor | None = None, bad: torch.Tensor | None = None, eps: float = 1e-6):
+    """Prior-aware retrieval (include/vfr.h vfr_score_prior_f32): moments ranked by fl(score + table entry), moments whose entry is
+    +inf excluded.  ``table``: an ``engine.MomentTable`` on the device (``engine.moment_table`` / ``engine.prior_table``).
+    ``level`` "moments": the k best candidate moments; "videos": the k best videos that have a candidate, each as (best biased
+    score, id of that moment).  Padded with (+inf, -1).  rank_dist / rank_idx [R, Nq] (or [Nq]), R <= 4: ``count_lt`` [R, Nq] int64
+    += the candidates (videos) that sort before each rank key (allocated zeroed when None); the key (+inf, -1) counts them all.
+    ``bad`` (int32 [1], optional) is set to 1 by an entry that is NaN or < 0.
+    Returns (dist [Nq,k] | None, idx [Nq,k] int64 | None, count_lt | None)."""
+    if level not in FUSION_LEVELS:
+        raise ValueError(f"score_prior: unknown level {level!r} (moments, videos)")
+    Q = _dev(Q, torch.float32, "Q")
+    if Q.dim() != 2 or Q.shape[1] != bank.dim:
+        raise ValueError(f"score_prior: Q must be [Nq, {bank.dim}], got {tuple(Q.shape)}")
+    Nq, dev = Q.shape[0], Q.device
+    off, val = _prior_table(table, bank, dev, "score_prior")
+    od, oi = _out_lists(Nq, k, dev)
+    rank_dist, rank_idx, count_lt, R = _rank_keys(rank_dist, rank_idx, count_lt, Nq, dev)
+    nbytes = lib().vfr_score_prior_workspace_bytes(Nq, bank.num_videos, k)
+    workspace = _workspace(workspace, nbytes, dev)
+    workspace._vfr_bank = None                   # whatever a pre-filter left in this workspace is overwritten
+    _check(lib().vfr_score_prior_f32(*_bank_args(Q, bank, eps), FUSION_LEVELS[level], k, _ptr(od), _ptr(oi), R, _ptr(rank_dist),
+                                     _ptr(rank_idx), _ptr(count_lt), off.data_ptr(), val.data_ptr(), _ptr(bad), workspace.data_ptr(),
+                                     nbytes, _stream()), "vfr_score_prior_f32")
     return od, oi, count_lt
 
 

@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ._vfr import KEY_EMPTY as KEY_INF, csr_offsets, fusion_weight_grid, fusion_weights   # (does not load libvfr.so)  KEY_INF = key of (+inf, max id): "no positive moment here"
+from ._vfr import KEY_EMPTY as KEY_INF, csr_offsets, fusion_weight_grid, fusion_weights, table_offsets   # (does not load libvfr.so)  KEY_INF = key of (+inf, max id): "no positive moment here"
 from .utils import generate_moments, get_iou
 
 
@@ -97,6 +97,12 @@ class HipOps:
 
     def score_fusion_sweep(self, Qs, banks, grid, level, rank_dist, rank_idx, count_lt=None):
         return self.v.score_fusion_sweep(Qs, banks, grid, level, rank_dist, rank_idx, count_lt=count_lt)
+
+    def score_prior(self, Q, bank, table, k, level="moments", rank_dist=None, rank_idx=None, count_lt=None, workspace=None, bad=None):
+        return self.v.score_prior(Q, bank, table, k, level, rank_dist, rank_idx, count_lt=count_lt, workspace=workspace, bad=bad)
+
+    def score_prior_own(self, Q, bank, table, own_local, bad=None):
+        return self.v.score_prior_own(Q, bank, table, own_local, bad=bad)
 
     def slice_bank(self, bank, counts, v0, v1):
         return self.v.slice_bank(bank, counts, v0, v1)
@@ -989,6 +995,192 @@ def corpus_fusion_sweep(fused: FusedCorpus, Qs, grid, level="moments", own_globa
     return cnt[:, 0] if level == "videos" else cnt
 
 
+PRIOR_MAX_CLIPS = 64                          # include/vfr.h: max_clips <= 64
+
+
+@dataclass
+class MomentTable:
+    """A moment table of prior-aware retrieval (include/vfr.h): for every clip count n in 0 .. ``max_clips`` and every local moment
+    in ``generate_moments(n)`` order one fp32 entry -- a finite bias >= 0 added to the moment's score, or +inf = excluded.
+    ``values``: the host array; ``table_off`` int32 [max_clips + 2] / ``table`` fp32: the arrays the kernels read, on one device
+    (``on(device)`` gives the table there).  Built by ``moment_table`` / ``prior_table``."""
+    max_clips: int
+    values: np.ndarray
+    table_off: torch.Tensor
+    table: torch.Tensor
+
+    def row(self, n):
+        """The entries of n-clip videos, fp32 [n (n + 1) / 2] (a view of ``values``)."""
+        off = table_offsets(self.max_clips)
+        if not 0 <= n <= self.max_clips:
+            raise ValueError(f"MomentTable: no row for {n} clips (0 .. {self.max_clips})")
+        return self.values[int(off[n]):int(off[n + 1])]
+
+    def enabled(self, n):
+        """bool [n (n + 1) / 2]: which moments of an n-clip video are candidates (entry < +inf)."""
+        return self.row(n) < np.inf
+
+    def on(self, device):
+        device = torch.device(device)
+        if self.table.device == device:
+            return self
+        return MomentTable(self.max_clips, self.values, self.table_off.to(device), self.table.to(device))
+
+
+def _moment_table(max_clips, values, device, who):
+    """Checked fp32 entries -> MomentTable on ``device`` (None: the host)."""
+    v64 = np.asarray(values, np.float64)
+    with np.errstate(over="ignore"):
+        v32 = v64.astype(np.float32) + np.float32(0.0)                            # (-0 -> +0)
+    if np.isnan(v32).any() or (v32 < 0).any():
+        raise ValueError(f"{who}: an entry is NaN, negative or -inf (a bias is finite and >= 0; +inf excludes the moment)")
+    if (np.isinf(v32) & np.isfinite(v64)).any():
+        raise ValueError(f"{who}: a finite bias overflows fp32")
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    return MomentTable(int(max_clips), v32, torch.from_numpy(table_offsets(max_clips)).to(dev), torch.from_numpy(v32).to(dev))
+
+
+def moment_table(max_clips, bias=None, min_len=1, max_len=None, lengths=None, stride=1, device=None) -> MomentTable:
+    """A moment table for videos of up to ``max_clips`` clips (<= 64): zeros by default.  ``bias``: a callable
+    ``(n, start, end) -> float`` or a dict ``n -> array`` of n (n + 1) / 2 values in ``generate_moments(n)`` order (clip counts the
+    dict does not name get zeros).  A moment (start, end) is EXCLUDED (+inf) when its length end - start + 1 is outside
+    [``min_len``, ``max_len``], or not in ``lengths`` (when given), or ``start % stride != 0`` -- sliding-window proposal sets and
+    length limits.  ValueError for an entry that is NaN, negative or -inf."""
+    max_clips = int(max_clips)
+    if not 0 <= max_clips <= PRIOR_MAX_CLIPS:
+        raise ValueError(f"moment_table: max_clips = {max_clips} (0 .. {PRIOR_MAX_CLIPS})")
+    if int(stride) < 1 or int(min_len) < 0:
+        raise ValueError(f"moment_table: stride = {stride} (>= 1), min_len = {min_len} (>= 0)")
+    allowed = None if lengths is None else {int(x) for x in lengths}
+    rows = []
+    for n in range(max_clips + 1):
+        spans = generate_moments(n)
+        if bias is None:
+            row = np.zeros(len(spans), np.float64)
+        elif callable(bias):
+            row = np.asarray([float(bias(n, s, e)) for s, e in spans], np.float64).reshape(len(spans))
+        else:
+            row = np.asarray(bias[n], np.float64).reshape(-1).copy() if n in bias else np.zeros(len(spans), np.float64)
+            if len(row) != len(spans):
+                raise ValueError(f"moment_table: bias[{n}] has {len(row)} entries, an {n}-clip video has {len(spans)} moments")
+        for j, (s, e) in enumerate(spans):
+            length = e - s + 1
+            if (length < min_len or (max_len is not None and length > max_len) or (allowed is not None and length not in allowed)
+                    or s % int(stride) != 0):
+                if np.isnan(row[j]) or row[j] < 0:                            # a bad bias stays an error under the mask
+                    raise ValueError("moment_table: an entry is NaN, negative or -inf")
+                row[j] = np.inf
+        rows.append(row)
+    return _moment_table(max_clips, np.concatenate(rows) if rows else np.zeros(0), device, "moment_table")
+
+
+def prior_table(times, counts, lam=1.0, alpha=1.0, max_clips=None, device=None) -> MomentTable:
+    """The temporal prior of the training annotations as a penalty table: ``times[i]`` = the annotator spans (start, end) of
+    training annotation i, ``counts[i]`` = the clip count of its video.  Per clip count n seen in training, with c[j] = how often
+    moment j of ``generate_moments(n)`` was annotated, total = sum c and M = n (n + 1) / 2:
+
+        entry(n, j) = fp32(lam * -log((c[j] + alpha) / (total + alpha * M)))
+
+    -- ``lam`` x the negative log of the add-``alpha`` smoothed frequency, >= 0.  Clip counts never seen in training get zeros.
+    ``alpha`` = 0 gives +inf for a moment nobody annotated: it is never proposed.  EVERY span of every annotation is counted; the
+    reference's ``moment_frequency`` loop (``model/evaluate.py``) skips the first annotation it meets of each clip count.  Spans
+    that do not lie inside their video (end >= n, start > end) are ignored."""
+    counts = np.asarray(counts, np.int64).reshape(-1)
+    if len(times) != len(counts):
+        raise ValueError(f"prior_table: {len(times)} annotations with {len(counts)} clip counts")
+    if not (np.isfinite(lam) and lam >= 0 and np.isfinite(alpha) and alpha >= 0):
+        raise ValueError(f"prior_table: lam = {lam}, alpha = {alpha} (finite, >= 0)")
+    if max_clips is None:
+        max_clips = int(counts.max()) if len(counts) else 0
+    max_clips = int(max_clips)
+    if not 0 <= max_clips <= PRIOR_MAX_CLIPS:
+        raise ValueError(f"prior_table: max_clips = {max_clips} (0 .. {PRIOR_MAX_CLIPS})")
+    off = table_offsets(max_clips).astype(np.int64)
+    freq = np.zeros(int(off[-1]), np.float64)
+    for spans, n in zip(times, counts.tolist()):
+        if not 0 < n <= max_clips:
+            continue
+        for s, e in spans:
+            s, e = int(s), int(e)
+            if 0 <= s <= e < n:
+                freq[off[n] + (s if s == e else n + (s * (2 * n - s - 1)) // 2 + (e - s - 1))] += 1
+    values = np.zeros_like(freq)
+    for n in range(1, max_clips + 1):
+        c = freq[off[n]:off[n + 1]]
+        total = c.sum()
+        if total == 0:
+            continue
+        with np.errstate(divide="ignore"):
+            pen = -np.log((c + alpha) / (total + alpha * len(c)))
+        values[off[n]:off[n + 1]] = np.where(np.isinf(pen), np.inf, float(lam) * np.where(np.isinf(pen), 0.0, pen))
+    return _moment_table(max_clips, values, device, "prior_table")
+
+
+def _enabled_rows(table: MomentTable, n_own, Mmax):
+    """bool [Nq, Mmax]: the candidate moments of each query's own video (``n_own`` clips), False past its moments."""
+    n_own = np.asarray(n_own, np.int64)
+    out = np.zeros((len(n_own), Mmax), bool)
+    for n in np.unique(n_own):
+        en = table.enabled(int(n))[:Mmax]
+        out[np.nonzero(n_own == n)[0], :len(en)] = en
+    return out
+
+
+def corpus_prior_topk(shard: CorpusShard, Q, table: MomentTable, k, level="moments", own_global=None, labels=None, ops=None, world=1,
+                      workspace=None):
+    """Prior-aware retrieval over the corpus: every moment is ranked by fl(score + table entry) and the moments ``table`` excludes
+    (+inf) are no candidates (``moment_table`` / ``prior_table``; include/vfr.h states the arithmetic).  ``level`` "moments": the k
+    best candidate moments; "videos": the k best videos that have a candidate, each as its best one.  A video never spans shards,
+    so the lists merge with the moment-key merge and the counts add.
+    Ground truth: "moments" with ``own_global`` and ``labels`` [R, Nq, Mmax] (``gt_labels``) -> ranks [R, Nq] = 0-based position of
+    the best positive CANDIDATE in the biased order; "videos" with ``own_global`` -> ranks [Nq] = videos whose best candidate key
+    sorts before the own video's.  The labels are ANDed with ``table.enabled`` of the own video first.  A query whose every positive
+    is excluded does not raise: its rank is the number of candidates (videos with one) in the corpus -- no k finds it -- and it is
+    marked in ``unreachable`` (bool, the shape of ranks): the proposal-recall ceiling of a sliding-window protocol.  A query
+    without a positive moment before the mask raises IndexError as ``corpus_ranks``.
+    Returns (dist [Nq,k], moment id [Nq,k] int64, video index [Nq,k] int64 (-1 = padding), ranks | None, unreachable | None);
+    lists are None for k = 0."""
+    ops = ops or HipOps()
+    if level not in ("moments", "videos"):
+        raise ValueError(f"corpus_prior_topk: unknown level {level!r} (moments, videos)")
+    if table.max_clips < (int(shard.counts_all.max()) if len(shard.counts_all) else 0):
+        raise ValueError(f"corpus_prior_topk: the moment table covers videos of up to {table.max_clips} clips, the corpus has "
+                         f"{int(shard.counts_all.max())}")
+    table = table.on(shard.device)
+    Nq = Q.shape[0]
+    gt = None
+    if own_global is not None and (level == "videos" or labels is not None):
+        own = np.asarray(own_global, np.int64)
+        n_own = np.asarray(shard.counts_all, np.int64)[own]
+        if level == "videos":
+            nmax = int(n_own.max()) if Nq else 0
+            labels = _enabled_rows(table, n_own, nmax * (nmax + 1) // 2)[None]
+        else:
+            if bool((~labels.any(-1)).any()):
+                raise_no_positive()
+            en = _enabled_rows(table, n_own, labels.shape[2])[None]
+            labels = labels & (torch.from_numpy(en).to(labels.device) if isinstance(labels, torch.Tensor) else en)
+        gt = prepare_gt(shard, own, labels)
+    rd = ri = unreachable = None
+    if gt is not None:
+        if gt.sel is not None:
+            sc = ops.score_prior_own(Q if gt.all_local else Q[gt.sel].contiguous(), shard.bank, table, gt.own_local)
+            keys = ops.gt_best_keys(sc, gt.labels, gt.base, gt.sel, Nq)
+        else:
+            keys = torch.full((gt.num_thresholds, Nq), KEY_INF, dtype=torch.int64, device=shard.device)
+        dist = _group(world)
+        if dist is not None:
+            dist.all_reduce(keys, op=dist.ReduceOp.MIN)
+        unreachable = keys == KEY_INF
+        rd, ri = _unpack_key(keys)
+        rd, ri = rd.contiguous(), ri.contiguous()
+    od, oi, cnt = _exchange(*ops.score_prior(Q, shard.bank, table, k, level, rd, ri, workspace=workspace), k, ops, world)
+    vid = _video_of(shard, oi) if k > 0 else None
+    if cnt is not None and level == "videos":
+        cnt, unreachable = cnt[0], unreachable[0]
+    return od, oi, vid, cnt, unreachable
+
+
 def corpus_sentence_topk(shard: CorpusShard, S, probes, k, own_sentence=None, ops=None, world=1, workspace=None):
     """Sentence retrieval for moments over the corpus: per probe ``(global video, start_t, end_t)`` (inclusive clip span,
     ``utils.generate_moments`` units; host array-like [Nm, 3]) the k sentences of the bank ``S`` [Ns, D] with the smallest mean clip
@@ -1609,6 +1801,56 @@ class TorchCpuOps:
                              f"{tuple(rank_idx.shape)}")
         return torch.stack([self.score_fusion(Qs, banks, grid[w], 0, level, rank_dist[w], rank_idx[w],
                                               None if count_lt is None else count_lt[w], eps=eps)[2] for w in range(W)])
+
+    @staticmethod
+    def _biased(sc, bias, bad):
+        """g = fl(score + entry) as float32 numpy, +inf where the entry is NaN or < 0 (reported in ``bad``): ONE float32 addition on
+        the provider's dense scores, so the CPU device carries the prior kernels' bits."""
+        wrong = ~(bias >= 0)
+        if wrong.any() and bad is not None:
+            bad.fill_(1)
+        with np.errstate(invalid="ignore"):
+            g = np.add(sc, np.where(wrong, np.float32(np.inf), bias)[None, :], dtype=np.float32)
+        return g
+
+    def score_prior_own(self, Q, bank, table, own_local, bad=None, eps=1e-6):
+        """Biased scores of each query against its own video: the layout of ``score_own``, +inf at excluded moments (same semantics
+        as ``_vfr.score_prior_own``)."""
+        counts = bank.counts
+        nmax = max(counts) if counts else 0
+        if table.max_clips < nmax:
+            raise ValueError(f"score_prior_own: the moment table covers videos of up to {table.max_clips} clips, the bank has {nmax}")
+        out = torch.full((Q.shape[0], nmax * (nmax + 1) // 2), float("inf"))
+        off = bank.clip_off.tolist()
+        for q, v in enumerate(own_local.tolist()):
+            if not 0 <= v < len(counts):
+                continue
+            sc = self._video_scores(self._clip_dist(Q[q:q + 1], bank.emb[off[v]:off[v + 1]], eps)).numpy()
+            out[q, :sc.shape[1]] = torch.from_numpy(self._biased(sc, table.row(counts[v]), bad)[0])
+        return out
+
+    def score_prior(self, Q, bank, table, k, level="moments", rank_dist=None, rank_idx=None, count_lt=None, workspace=None, bad=None,
+                    eps=1e-6):
+        """Prior-aware retrieval from dense scores (same semantics as ``_vfr.score_prior``): the dense scores, one float32 addition of
+        the table entries, keys (biased score, global id) of the candidates (g < +inf; the others become KEY_INF, which sorts last,
+        is never below a rank key and turns into padding); moments, or each video's smallest candidate key."""
+        if level not in ("moments", "videos"):
+            raise ValueError(f"score_prior: unknown level {level!r} (moments, videos)")
+        counts = bank.counts
+        if table.max_clips < (max(counts) if counts else 0):
+            raise ValueError(f"score_prior: the moment table covers videos of up to {table.max_clips} clips, the bank has {max(counts)}")
+        Nq = Q.shape[0]
+        sc = self._dense(Q, bank, eps).numpy()
+        bias = np.concatenate([table.row(n) for n in counts]) if counts else np.zeros(0, np.float32)
+        g = torch.from_numpy(self._biased(sc, bias, bad))
+        keys = _pack_key(g, (bank.id_base + torch.arange(g.shape[1]))[None, :].expand_as(g))
+        keys = torch.where(g < float("inf"), keys, torch.full_like(keys, KEY_INF))
+        if level == "videos":
+            mo = csr_offsets(counts)[1]
+            best = [keys[:, int(a):int(b)].min(dim=1).values for a, b in zip(mo[:-1], mo[1:]) if b > a]
+            keys = torch.stack(best, dim=1) if best else torch.zeros((Nq, 0), dtype=torch.int64)
+        kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nq), rank_idx.reshape(-1, Nq))
+        return self._topk_lists(keys, k) + (self._counts_below(keys, kstar, count_lt),)
 
     def score_sentences(self, S, bank, probes, k, vid_base=0, sent_base=0, rank_dist=None, rank_idx=None, count_lt=None, bad=None,
                         workspace=None, eps=1e-6):

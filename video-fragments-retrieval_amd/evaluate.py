@@ -494,3 +494,42 @@ def sweep_fusion(models, video_iterators, lang_iterators, annotations, device, g
         vals = [m[key][name] for m in metrics]
         best = int(np.argmin(vals) if name == "MR" else np.argmax(vals))          # argmin / argmax: the first of equal values
     return metrics, best
+
+
+def evaluate_prior(model, video_iterator, lang_iterator, annotations, device, table, level="moments", atk=(1, 10, 100),
+                   iou_thresholds=(0.5, 0.7), rank=0, world=1, k=0):
+    """Retrieval metrics under a moment table (``engine.moment_table`` / ``engine.prior_table``): every moment is ranked by its
+    score plus the table's bias and the moments the table excludes are no candidates (``engine.corpus_prior_topk``) -- "prior +
+    model" of the papers, sliding-window proposal protocols, length limits.
+
+    ``level`` "moments": per IoU threshold the 0-based rank of the best ground-truth-positive CANDIDATE in the biased order ->
+    ``{"model, IoU=<thr>": {"R@1", "R@10", "R@100", "MR"}}`` in ``evaluate``'s key format (strict labels; a query without a
+    positive moment raises IndexError); "videos": the rank of the own video's best candidate key -> ``{"video": {...}}`` as
+    ``evaluate_videos``.  A query whose every positive moment is excluded is never found: its rank is the number of candidates.  The
+    share of such queries is reported next to the metrics, ``out["unreachable"] = {"IoU=<thr>": percent}`` (``{"video": percent}``)
+    -- 100 minus it is the recall ceiling of the proposal set.  With a table of zeros the other entries equal ``evaluate``'s
+    (``evaluate_videos``'s) and every share is 0.  ``k`` > 0 also returns ``(dist, moment idx, video idx)`` [Nq, k]."""
+    if level not in ("moments", "videos"):
+        raise ValueError(f"evaluate_prior: unknown level {level!r} (moments, videos)")
+    K = int(k)
+    with _eval_mode(model):
+        ops, _, annot_ids, shard, names, Q, own = _prepare(model, video_iterator, lang_iterator, device, rank, world)
+        if shard is None:
+            out = _fusion_empty(level, atk, iou_thresholds)
+            out["unreachable"] = {"video": 0.0} if level == "videos" else {f"IoU={thr}": 0.0 for thr in iou_thresholds}
+            return (out, (None, None, None)) if K else out
+        if level == "videos":
+            dist, idx, vid, ranks, unreach = engine.corpus_prior_topk(shard, Q, table, K, "videos", own_global=own, ops=ops, world=world)
+            out = {"video": get_metrics(_rank_metrics(ranks.cpu().numpy(), atk)),
+                   "unreachable": {"video": float(unreach.float().mean()) * 100}}
+        else:
+            times = [annotations[a]["times"] for a in annot_ids]
+            labels = engine.gt_labels(times, shard.counts_all[own], list(iou_thresholds), True, shard.device, ops)
+            dist, idx, vid, ranks, unreach = engine.corpus_prior_topk(shard, Q, table, K, "moments", own_global=own, labels=labels,
+                                                                      ops=ops, world=world)
+            ranks, unreach = ranks.cpu().numpy(), unreach.cpu().numpy()
+            out = {f"model, IoU={thr}": get_metrics(_rank_metrics(ranks[r], atk)) for r, thr in enumerate(iou_thresholds)}
+            out["unreachable"] = {f"IoU={thr}": float(unreach[r].mean()) * 100 for r, thr in enumerate(iou_thresholds)}
+    if K:
+        return out, (dist, idx, vid)
+    return out
