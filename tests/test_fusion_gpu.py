@@ -102,9 +102,12 @@ def check(vfr, Scs, Qs, Vs, counts, off, w, ks, levels=LEVELS, id_base=0, what="
 
 @pytest.mark.parametrize("nv", [1, 2, 63, 64, 65, 130])
 def test_chunk_edges(vfr, oracle, nv):
-    """Banks that end before, on and after a chunk of 64 videos; clip counts mixed 1..21 with 21 first and last; S = 2."""
+    """Banks that end before, on and after a chunk of 64 videos; clip counts mixed 1..21 with 21 first and last; S = 2.
+    Nv = 130 also takes k on both sides of the list capacities (128 | 256 slots at k = 64 | 65, 256 | 512 at k = 192 | 193): a block
+    of 64 videos emits over a thousand keys, so the list fills and is cut back at every capacity."""
     Qs, Vs, counts, off = streams(mixed_counts(nv, nv), seed=nv)
-    check(vfr, dense(oracle, Qs, Vs, off), Qs, Vs, counts, off, (0.7, 0.3), (0, 1, 16, 448), what=f"Nv = {nv}")
+    ks = (0, 1, 16, 448) + ((64, 65, 192, 193) if nv == 130 else ())
+    check(vfr, dense(oracle, Qs, Vs, off), Qs, Vs, counts, off, (0.7, 0.3), ks, what=f"Nv = {nv}")
 
 
 def test_long_videos(vfr, oracle):

@@ -90,7 +90,8 @@ def mixed_counts(nv, seed):
 @pytest.mark.parametrize("nv", [1, 2, 63, 64, 65, 130])
 def test_chunk_edges_and_own_video_positions(vfr, oracle, nv):
     """Banks that end before, on and after a chunk of 64 videos, clip counts mixed 1..21 (many videos shorter than e + 1), the own
-    video first, at both sides of a chunk edge and last."""
+    video first, at both sides of a chunk edge and last.  Nv = 130 also takes h on both sides of the inter list's capacities (128 |
+    256 slots at h = 64 | 65, 256 | 512 at h = 192 | 193)."""
     counts = mixed_counts(nv, nv)
     for v in (63, 64):
         if v < nv:
@@ -102,8 +103,9 @@ def test_chunk_edges_and_own_video_positions(vfr, oracle, nv):
     items = np.concatenate([random_items(rs, counts, 12, len(Q), vids=owns), random_items(rs, counts, 20, len(Q))])
     pos, _ = span_scores(Sc, counts, items)
     thr = (pos + np.float32(0.1)).astype(np.float32)
+    hs = (0, 1, 16) + ((64, 65, 192, 193) if nv == 130 else ())
     for mode in ("same_length", "any"):
-        check(vfr, Sc, Q, V, counts, off, items, (0, 1, 16), mode, thr=thr, what=f"Nv = {nv}")
+        check(vfr, Sc, Q, V, counts, off, items, hs, mode, thr=thr, what=f"Nv = {nv}")
 
 
 @pytest.mark.parametrize("nm", [0, 1, 65])
@@ -142,7 +144,8 @@ def test_streams_of_several_blocks_per_wave(vfr, oracle):
     """2 100 items against 1 100 videos: the video axis is cut into 2 chunks of 576 and 524 videos, so one wave streams 9 blocks of
     64 videos under its running threshold -- the list fills and is sorted and cut back to h inside the loop (h = 1 and 16 after two
     blocks, h = 448 after eight), later keys are tested against the threshold, and the last block of a chunk is partial.  Tied
-    videos sit in different blocks of one chunk and in different chunks."""
+    videos sit in different blocks of one chunk and in different chunks.  h = 64 | 65 and 192 | 193 sit on both sides of the list
+    capacities (128 | 256 and 256 | 512 slots): here, unlike at Nv = 130, each of those lists fills and is cut back."""
     lib = vfr.lib()
     nv, distinct, rep = 1100, 60, 35
     assert lib.vfr_mine_negatives_workspace_bytes(distinct * rep, nv, 448) == 256 + 2 * distinct * rep * 448 * 8      # 2 chunks
@@ -161,7 +164,7 @@ def test_streams_of_several_blocks_per_wave(vfr, oracle):
     pos, _ = span_scores(Sc, counts, base)
     floor = np.where(np.arange(distinct) % 2 == 0, pos, np.float32(0)).astype(np.float32)
     thr = (pos + np.float32(0.1)).astype(np.float32)
-    for h in (1, 16, 448):
+    for h in (1, 16, 64, 65, 192, 193, 448):
         want = statement(Sc, counts, base, h, floor=floor, thr=thr)
         got = run(vfr, Q, V, off, items, h, floor=floor[pick], thr=thr[pick])
         assert got["bad"] == 0

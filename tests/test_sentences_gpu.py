@@ -82,12 +82,14 @@ def check(vfr, block, S, V, counts, off, probes, ks, Rs=(0, 2), vid_base=0, sent
 
 @pytest.mark.parametrize("ns", [1, 63, 64, 65, 5000])
 def test_bank_sizes_and_k(vfr, oracle, ns):
-    """Ns in {1, 63, 64, 65, 5000} x k in {0, 1, 10, 100, 448} (k > Ns pads) x 0..4 rank keys."""
+    """Ns in {1, 63, 64, 65, 5000} x k in {0, 1, 10, 100, 448} (k > Ns pads) x 0..4 rank keys.  Ns = 65 also takes k on both sides
+    of the list capacities (128 | 256 slots at k = 64 | 65, 256 | 512 at k = 192 | 193)."""
     V, counts, off = corpus(synth.clip_counts(40, "didemo", seed=3), seed=3)
     S = sentences(ns, seed=4)
     probes = random_probes(np.random.RandomState(5), counts, 37)
     block = dense_blocks(oracle.score_moments(S, V, off), counts)
-    check(vfr, block, S, V, counts, off, probes, (0, 1, 10, 100, 448), Rs=(0, 1, 2, 3, 4))
+    ks = (0, 1, 10, 100, 448) + ((64, 65, 192, 193) if ns == 65 else ())
+    check(vfr, block, S, V, counts, off, probes, ks, Rs=(0, 1, 2, 3, 4))
 
 
 def test_all_moments_of_shared_videos(vfr, oracle):

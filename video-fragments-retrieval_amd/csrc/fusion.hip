@@ -3,7 +3,7 @@
 // S <= 4 streams (feature types, modalities, seeds) describe the same videos: stream s has its own clip bank V_s [total_clips, D_s],
 // its own query matrix Q_s [Nq, D_s] and a weight w_s >= 0; clip_offsets / moment_offsets are shared.  The ranking key changes at
 // the CLIP: d_s[q, c] is the canonical chain of vfr_score_moments_f32 (k-ascending fp32 fma chain of ((v - q) + eps)^2, IEEE sqrt),
-// restated here so the code objects of score.o do not change; the fused clip distance is
+// written out in fus_dist (not taken from the headers of score.o, so its code objects do not change); the fused clip distance is
 //     f = fl(w_0 d_0);  f = fl(f + fl(w_s d_s)), s = 1 .. S-1          (__fmul_rn / __fadd_rn: every operation rounded, no fma)
 // and everything downstream is the existing moment chain on f: sequential fp32 sum s -> e started at f[s], one IEEE division by
 // (float)(e - s + 1), key = (score bits << 32) | (id_base + moment_offsets[v] + position in utils.generate_moments order).  The
@@ -20,44 +20,18 @@
 //                       triangle) are collected under a running threshold into an LDS list of 128 / 256 / 512 keys that is sorted
 //                       and cut back to k when it fills; the chunk's list goes to ws[chunk][query][0..k).
 //   The per-chunk lists are merged by vfr_topk_merge_keys (one launch), which also pads with (+inf, -1).
-// The video axis is cut into at most FUS_MAX_CHUNKS chunks, just enough for about FUS_TARGET_WAVES waves (one query against
-// 10 000 videos fills the device, 5 000 queries run whole-bank streams: a running threshold wants long streams).
-// Workspace: chunks x Nq x k keys, chunks <= FUS_MAX_CHUNKS whatever Nv is.  Nothing is of size Nq x Nv, nothing waits for the host.
-#include "vfr_common.h"
-#include "vfr_math.h"
+// The chunk plan (scan_plan: at most SCAN_MAX_CHUNKS chunks, just enough for about SCAN_TARGET_WAVES waves -- one query against
+// 10 000 videos fills the device, 5 000 queries run whole-bank streams: a running threshold wants long streams), the list's
+// capacity and sort and the scan kernel's rank-key counters are those of scan_common.h.
+// Workspace: chunks x Nq x k keys, chunks <= SCAN_MAX_CHUNKS whatever Nv is.  Nothing is of size Nq x Nv, nothing waits for the host.
+#include "scan_common.h"
 
 namespace vfr {
 namespace {
 
 constexpr int FUS_MAX_S = VFR_FUSION_MAX_STREAMS;
 constexpr int FUS_MAX_CLIPS = 64;                    // as the fused scorer
-constexpr int FUS_MAX_K = 448;
-constexpr int FUS_MAX_RANK = 4;
 constexpr int FUS_MAX_SUM_D = VFR_FUSION_MAX_SUM_D;  // floats of query rows in LDS (each D_s rounded up to 4)
-constexpr int FUS_MAX_CHUNKS = 256;
-constexpr int FUS_TARGET_WAVES = 4096;
-constexpr unsigned long long FUS_KEY_MAX = ~0ull;
-constexpr unsigned long long FUS_KEY_EMPTY = 0x7F800000FFFFFFFFull;   // VFR_KEY_EMPTY: an unused slot of a list
-
-// slots of a scan wave's LDS list: a power of two >= k + 64 (a wave appends up to 64 keys before it looks at the fill)
-int fus_cap(int k) { return k == 0 ? 0 : k <= 64 ? 128 : k <= 192 ? 256 : 512; }
-
-struct FusPlan { int chunks; int64_t per; int bound; };
-// chunks = min(ceil(FUS_TARGET_WAVES / Nq), blocks of 64 videos, FUS_MAX_CHUNKS), evened out; `bound` (what the workspace is sized
-// by) does not look at Nv beyond "fewer blocks than that"
-FusPlan fus_plan(int64_t Nq, int64_t Nv)
-{
-    FusPlan p{};
-    const int64_t blocks = cdiv(Nv, 64);
-    int64_t want = cdiv(FUS_TARGET_WAVES, Nq > 0 ? Nq : 1);
-    want = want > FUS_MAX_CHUNKS ? FUS_MAX_CHUNKS : want;
-    int64_t c = want < blocks ? want : blocks;
-    c = c < 1 ? 1 : c;
-    p.bound = (int)c;
-    p.per = cdiv(blocks > 0 ? blocks : 1, c) * 64;
-    p.chunks = (int)cdiv(Nv > 0 ? Nv : 1, p.per);
-    return p;
-}
 
 // the streams, by value in the kernel arguments: device pointers, widths, weights, where each query row starts in LDS
 struct FusStreams {
@@ -69,13 +43,6 @@ struct FusStreams {
     float w[FUS_MAX_S];
     int S;
     int qs_floats;               // sum of the rows, each rounded up to 4 floats
-};
-
-struct FusRank {
-    int num_rank;
-    const float *dist;           // [num_rank, Nq]
-    const int64_t *idx;
-    int64_t *count_lt;
 };
 
 // one clip row against the query row in LDS: the canonical chain
@@ -128,25 +95,6 @@ __device__ __forceinline__ void fus_query_rows(const FusStreams &st, int64_t q, 
     __syncthreads();
 }
 
-// bitonic sort of b[0..size) (slots >= cnt filled with KEY_MAX first), one wave; size a power of two >= cnt
-__device__ __forceinline__ void fus_sort(unsigned long long *b, int cnt, int size, int lane)
-{
-    for (int i = cnt + lane; i < size; i += 64) b[i] = FUS_KEY_MAX;
-    __syncthreads();
-    for (int sz = 2; sz <= size; sz <<= 1)
-        for (int stride = sz >> 1; stride > 0; stride >>= 1) {
-            for (int i = lane; i < size; i += 64) {
-                const int o = i ^ stride;
-                if (o > i) {
-                    const bool asc = (i & sz) == 0;
-                    const unsigned long long x = b[i], y = b[o];
-                    if ((x > y) == asc) { b[i] = y; b[o] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
 // ---- each query against ONE video own[q]: one wave per query; lane = clip, then lane = start clip ----
 __global__ __launch_bounds__(64) void fusion_own_kernel(const FusStreams st, int64_t Nq, const int32_t *__restrict__ clip_off,
                                                         const int32_t *__restrict__ own, int Nv, float eps, int Mmax,
@@ -184,7 +132,7 @@ __global__ __launch_bounds__(64) void fusion_own_kernel(const FusStreams st, int
 // ---- one wave per (query, chunk of the video axis), lane = video ----
 __global__ __launch_bounds__(64) void fusion_scan_kernel(const FusStreams st, int64_t Nq, const int32_t *__restrict__ clip_off,
                                                          const int64_t *__restrict__ mom_off, int Nv, float eps, int64_t id_base,
-                                                         int level, int k, int cap, FusRank rk, int ds_rows, int chunks, int64_t per,
+                                                         int level, int k, int cap, ScanRank rk, int ds_rows, int chunks, int64_t per,
                                                          unsigned long long *__restrict__ ws)
 {
     extern __shared__ __attribute__((aligned(16))) float ssm[];
@@ -196,16 +144,16 @@ __global__ __launch_bounds__(64) void fusion_scan_kernel(const FusStreams st, in
     const int ch = (int)(blockIdx.x - q * chunks);
     fus_query_rows(st, q, qs, lane);
 
-    unsigned long long rkey[FUS_MAX_RANK];
+    unsigned long long rkey[SCAN_MAX_RANK];
 #pragma unroll
-    for (int r = 0; r < FUS_MAX_RANK; ++r)
+    for (int r = 0; r < SCAN_MAX_RANK; ++r)
         rkey[r] = r < rk.num_rank ? make_key(rk.dist[r * Nq + q], (unsigned)rk.idx[r * Nq + q]) : 0ull;
-    int nlt[FUS_MAX_RANK] = {0, 0, 0, 0};
+    int nlt[SCAN_MAX_RANK] = {0, 0, 0, 0};
 
     const int64_t v0 = (int64_t)ch * per;
     const int64_t v1 = v0 + per < Nv ? v0 + per : Nv;
     const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    unsigned long long thr = FUS_KEY_MAX;                      // keys >= thr cannot be among the chunk's k smallest
+    unsigned long long thr = SCAN_KEY_MAX;                     // keys >= thr cannot be among the chunk's k smallest
     int cnt = 0;                                               // keys in buf (wave-uniform)
     // a wave-uniform append of the lanes' keys under the threshold; the list is sorted and cut back to k when it may overflow
     auto append = [&](bool take, unsigned long long key) {
@@ -215,7 +163,7 @@ __global__ __launch_bounds__(64) void fusion_scan_kernel(const FusStreams st, in
             cnt += __popcll(mt);
             if (cnt > cap - 64) {
                 __syncthreads();
-                fus_sort(buf, cnt, cap, lane);
+                wave_sort_keys(buf, cnt, cap, lane);
                 if (cnt >= k) { thr = buf[k - 1]; cnt = k; }
                 __syncthreads();
             }
@@ -234,7 +182,7 @@ __global__ __launch_bounds__(64) void fusion_scan_kernel(const FusStreams st, in
             for (int c = 0; c < n; ++c) ds[c * 64 + lane] = fus_clip(st, qs, (int64_t)c0 + c, eps);   // the lane's own column
         }
         if (level == VFR_FUSION_VIDEOS) {
-            unsigned long long best = FUS_KEY_EMPTY;
+            unsigned long long best = SCAN_KEY_EMPTY;
             for (int s = 0; s < n; ++s) {
                 float sum = 0.0f;
                 for (int e2 = s; e2 < n; ++e2) {
@@ -245,10 +193,7 @@ __global__ __launch_bounds__(64) void fusion_scan_kernel(const FusStreams st, in
                     best = key < best ? key : best;
                 }
             }
-            if (n > 0) {
-#pragma unroll
-                for (int r = 0; r < FUS_MAX_RANK; ++r) nlt[r] += (r < rk.num_rank && best < rkey[r]) ? 1 : 0;
-            }
+            if (n > 0) scan_rank_count(rk.num_rank, rkey, best, nlt);
             if (k > 0) append(n > 0 && best < thr, best);
         } else {
             // the wave-uniform loop over the widest triangle of the block: a lane past its own video's end takes no part
@@ -263,10 +208,7 @@ __global__ __launch_bounds__(64) void fusion_scan_kernel(const FusStreams st, in
                     sum = e2 == s ? de : sum + de;
                     const float sc = sum / (float)(e2 - s + 1);
                     const unsigned long long key = make_key(sc, (unsigned)(mbase + moment_index(n, s, e2)));
-                    if (live) {
-#pragma unroll
-                        for (int r = 0; r < FUS_MAX_RANK; ++r) nlt[r] += (r < rk.num_rank && key < rkey[r]) ? 1 : 0;
-                    }
+                    if (live) scan_rank_count(rk.num_rank, rkey, key, nlt);
                     if (k > 0) append(live && key < thr, key);
                 }
             }
@@ -276,14 +218,14 @@ __global__ __launch_bounds__(64) void fusion_scan_kernel(const FusStreams st, in
         __syncthreads();
         int size = 64;
         while (size < cnt) size <<= 1;                         // cnt <= cap, a power of two
-        fus_sort(buf, cnt, size, lane);
+        wave_sort_keys(buf, cnt, size, lane);
         cnt = cnt > k ? k : cnt;
         unsigned long long *out = ws + ((size_t)ch * Nq + q) * k;
-        for (int i = lane; i < k; i += 64) out[i] = i < cnt ? buf[i] : FUS_KEY_EMPTY;
+        for (int i = lane; i < k; i += 64) out[i] = i < cnt ? buf[i] : SCAN_KEY_EMPTY;
     }
     if (rk.num_rank > 0) {
 #pragma unroll
-        for (int r = 0; r < FUS_MAX_RANK; ++r) {
+        for (int r = 0; r < SCAN_MAX_RANK; ++r) {
             // a lane counts at most its share of the 2^32 ids, the wave's sum needs 64 bits (one wave may stream the whole bank)
             unsigned long long x = (unsigned long long)(unsigned)nlt[r];
 #pragma unroll
@@ -329,7 +271,7 @@ int fus_streams(const char *who, const float *const *Q_host, const float *const 
 // the single-weight kernels' at that vector.
 //   fusion_sweep_own_kernel  one wave per query, lane = clip of own[q]: its S distances stay in registers; per weight vector the lane
 //                            fuses them into an LDS row and, as start clip, walks the end clips (fusion_own_kernel's triangle).
-//   fusion_sweep_kernel      one wave per (query, chunk of the video axis) with the chunk plan of fus_plan, lane = video.  Per block
+//   fusion_sweep_kernel      one wave per (query, chunk of the video axis) with the chunk plan of scan_plan, lane = video.  Per block
 //                            of 64 videos the lane writes the PER-STREAM distances of its clips to LDS columns [S][rows][64]; then
 //                            the weight loop: fuse into one more column block [rows][64], walk the triangle, count the keys before
 //                            that weight's rank keys in num_rank <= 4 REGISTER counters, and flush them -- wave sum by shuffles,
@@ -410,7 +352,7 @@ __global__ __launch_bounds__(64) void fusion_sweep_own_kernel(const FusStreams s
 
 __global__ __launch_bounds__(64) void fusion_sweep_kernel(const FusStreams st, const FusGrid grid, int64_t Nq,
                                                           const int32_t *__restrict__ clip_off, const int64_t *__restrict__ mom_off,
-                                                          int Nv, float eps, int64_t id_base, int level, FusRank rk, int ds_rows,
+                                                          int Nv, float eps, int64_t id_base, int level, ScanRank rk, int ds_rows,
                                                           int chunks, int64_t per)
 {
     extern __shared__ __attribute__((aligned(16))) float ssm[];
@@ -457,13 +399,13 @@ __global__ __launch_bounds__(64) void fusion_sweep_kernel(const FusStreams st, c
                     if (s < st.S) d[s] = ds[s * blk + c * 64 + lane];
                 fs[c * 64 + lane] = fus_fuse(grid, wi, st.S, d);
             }
-            unsigned long long rkey[FUS_MAX_RANK];
+            unsigned long long rkey[SCAN_MAX_RANK];
 #pragma unroll
-            for (int r = 0; r < FUS_MAX_RANK; ++r) rkey[r] = r < rk.num_rank ? rkeys[wi * rk.num_rank + r] : 0ull;
-            int nlt[FUS_MAX_RANK] = {0, 0, 0, 0};
+            for (int r = 0; r < SCAN_MAX_RANK; ++r) rkey[r] = r < rk.num_rank ? rkeys[wi * rk.num_rank + r] : 0ull;
+            int nlt[SCAN_MAX_RANK] = {0, 0, 0, 0};
             // no list, so no wave-uniform step: every lane walks its own triangle
             if (level == VFR_FUSION_VIDEOS) {
-                unsigned long long best = FUS_KEY_EMPTY;
+                unsigned long long best = SCAN_KEY_EMPTY;
                 for (int s = 0; s < n; ++s) {
                     float sum = 0.0f;
                     for (int e2 = s; e2 < n; ++e2) {
@@ -476,7 +418,7 @@ __global__ __launch_bounds__(64) void fusion_sweep_kernel(const FusStreams st, c
                 }
                 if (n > 0) {
 #pragma unroll
-                    for (int r = 0; r < FUS_MAX_RANK; ++r) nlt[r] += (r < rk.num_rank && best < rkey[r]) ? 1 : 0;
+                    for (int r = 0; r < SCAN_MAX_RANK; ++r) nlt[r] += (r < rk.num_rank && best < rkey[r]) ? 1 : 0;
                 }
             } else {
                 for (int s = 0; s < n; ++s) {
@@ -487,13 +429,13 @@ __global__ __launch_bounds__(64) void fusion_sweep_kernel(const FusStreams st, c
                         const float sc = sum / (float)(e2 - s + 1);
                         const unsigned long long key = make_key(sc, (unsigned)(mbase + moment_index(n, s, e2)));
 #pragma unroll
-                        for (int r = 0; r < FUS_MAX_RANK; ++r) nlt[r] += (r < rk.num_rank && key < rkey[r]) ? 1 : 0;
+                        for (int r = 0; r < SCAN_MAX_RANK; ++r) nlt[r] += (r < rk.num_rank && key < rkey[r]) ? 1 : 0;
                     }
                 }
             }
             // flush: a block adds at most 64 x 2080 per (weight, rank), the totals are 64-bit (one wave may stream the whole bank)
 #pragma unroll
-            for (int r = 0; r < FUS_MAX_RANK; ++r) {
+            for (int r = 0; r < SCAN_MAX_RANK; ++r) {
                 if (r < rk.num_rank) {
                     int x = nlt[r];
 #pragma unroll
@@ -559,8 +501,8 @@ int vfr_score_fusion_own_f32(const float *const *Q_host, const float *const *V_h
 
 size_t vfr_score_fusion_workspace_bytes(int64_t Nq, int Nv, int k)
 {
-    if (Nq < 0 || Nv < 0 || k < 0 || k > vfr::FUS_MAX_K || Nq * (int64_t)(k > 0 ? k : 1) > 0x7FFFFFFF) return 0;
-    const vfr::FusPlan p = vfr::fus_plan(Nq, Nv);
+    if (Nq < 0 || Nv < 0 || k < 0 || k > vfr::SCAN_MAX_K || Nq * (int64_t)(k > 0 ? k : 1) > 0x7FFFFFFF) return 0;
+    const vfr::ScanPlan p = vfr::scan_plan(Nq, Nv, vfr::SCAN_TARGET_WAVES);
     return vfr::align_up((size_t)p.bound * (size_t)Nq * (size_t)k * 8 + 256, 256);
 }
 
@@ -576,18 +518,18 @@ int vfr_score_fusion_f32(const float *const *Q_host, const float *const *V_host,
     if (rc != VFR_OK) return rc;
     VFR_REQUIRE(level == VFR_FUSION_MOMENTS || level == VFR_FUSION_VIDEOS, VFR_EINVAL,
                 "vfr_score_fusion_f32: level %d (0 = moments, 1 = videos)", level);
-    VFR_REQUIRE(Nq >= 0 && Nv >= 0 && total_clips >= 0 && k >= 0 && k <= vfr::FUS_MAX_K && max_clips >= 0 &&
+    VFR_REQUIRE(Nq >= 0 && Nv >= 0 && total_clips >= 0 && k >= 0 && k <= vfr::SCAN_MAX_K && max_clips >= 0 &&
                 max_clips <= vfr::FUS_MAX_CLIPS && id_base >= 0, VFR_EINVAL,
                 "vfr_score_fusion_f32: bad shape (k <= 448, max_clips <= 64, sizes, id_base >= 0)");
     VFR_REQUIRE(id_base + (int64_t)total_clips * (max_clips + 1) / 2 <= (int64_t(1) << 32), VFR_EINVAL,
                 "vfr_score_fusion_f32: id_base + moments must stay below 2^32");
     VFR_REQUIRE(Nq * (int64_t)(k > 0 ? k : 1) <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_fusion_f32: Nq * k must stay below 2^31");
-    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::FUS_MAX_RANK, VFR_EINVAL, "vfr_score_fusion_f32: num_rank %d (0 .. 4)", num_rank);
+    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::SCAN_MAX_RANK, VFR_EINVAL, "vfr_score_fusion_f32: num_rank %d (0 .. 4)", num_rank);
     VFR_REQUIRE(num_rank == 0 || (rank_dist && rank_idx && count_lt), VFR_EINVAL,
                 "vfr_score_fusion_f32: num_rank > 0 needs rank_dist, rank_idx and count_lt");
     VFR_REQUIRE(k == 0 || Nq == 0 || (out_dist && out_idx), VFR_EINVAL, "vfr_score_fusion_f32: k > 0 needs out_dist / out_idx");
     VFR_REQUIRE(Nv == 0 || (clip_offsets && moment_offsets), VFR_EINVAL, "vfr_score_fusion_f32: null clip_offsets / moment_offsets");
-    const vfr::FusPlan plan = vfr::fus_plan(Nq, Nv);
+    const vfr::ScanPlan plan = vfr::scan_plan(Nq, Nv, vfr::SCAN_TARGET_WAVES);
     VFR_REQUIRE(Nq * plan.chunks <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_fusion_f32: too many (query, chunk) waves");
     const size_t need = vfr_score_fusion_workspace_bytes(Nq, Nv, k);
     VFR_REQUIRE(workspace && workspace_bytes >= need, VFR_EWORKSPACE, "vfr_score_fusion_f32: workspace %zu < %zu bytes", workspace_bytes,
@@ -598,9 +540,9 @@ int vfr_score_fusion_f32(const float *const *Q_host, const float *const *V_host,
     {
         vfr::ProfScope prof(vfr::SITE_SCORE_PAIRS, stq);
         const int rows = max_clips < 1 ? 1 : max_clips;
-        const int cap = vfr::fus_cap(k);
+        const int cap = vfr::scan_cap(k);
         const size_t lds = ((size_t)st.qs_floats + (size_t)rows * 64) * 4 + (size_t)cap * 8;     // <= 32 + 16 + 4 KB
-        vfr::FusRank rk{num_rank, rank_dist, rank_idx, count_lt};
+        vfr::ScanRank rk{num_rank, rank_dist, rank_idx, count_lt};
         hipLaunchKernelGGL(vfr::fusion_scan_kernel, dim3((unsigned)(Nq * plan.chunks)), dim3(64), lds, stq, st, Nq, clip_offsets,
                            moment_offsets, Nv, eps, id_base, level, k, cap, rk, rows, plan.chunks, plan.per, keys);
         VFR_CHECK_LAUNCH("fusion_scan_kernel");
@@ -654,11 +596,11 @@ int vfr_score_fusion_sweep_f32(const float *const *Q_host, const float *const *V
                 "%s: bad shape (max_clips <= 64, sizes, id_base >= 0)", who);
     VFR_REQUIRE(id_base + (int64_t)total_clips * (max_clips + 1) / 2 <= (int64_t(1) << 32), VFR_EINVAL,
                 "%s: id_base + moments must stay below 2^32", who);
-    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::FUS_MAX_RANK, VFR_EINVAL, "%s: num_rank %d (0 .. 4)", who, num_rank);
+    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::SCAN_MAX_RANK, VFR_EINVAL, "%s: num_rank %d (0 .. 4)", who, num_rank);
     VFR_REQUIRE(num_rank == 0 || (rank_dist && rank_idx && count_lt), VFR_EINVAL, "%s: num_rank > 0 needs rank_dist, rank_idx and count_lt",
                 who);
     VFR_REQUIRE(Nv == 0 || (clip_offsets && moment_offsets), VFR_EINVAL, "%s: null clip_offsets / moment_offsets", who);
-    const vfr::FusPlan plan = vfr::fus_plan(Nq, Nv);
+    const vfr::ScanPlan plan = vfr::scan_plan(Nq, Nv, vfr::SCAN_TARGET_WAVES);
     VFR_REQUIRE(Nq * plan.chunks <= 0x7FFFFFFF, VFR_EINVAL, "%s: too many (query, chunk) waves", who);
     const int rows = max_clips < 1 ? 1 : max_clips;
     const size_t lds = vfr::fus_sweep_lds(st, rows, W, num_rank);
@@ -669,7 +611,7 @@ int vfr_score_fusion_sweep_f32(const float *const *Q_host, const float *const *V
     if (Nq == 0 || Nv == 0 || num_rank == 0) return VFR_OK;
     hipStream_t stq = vfr::as_stream(stream);
     vfr::ProfScope prof(vfr::SITE_SCORE_PAIRS, stq);
-    vfr::FusRank rk{num_rank, rank_dist, rank_idx, count_lt};
+    vfr::ScanRank rk{num_rank, rank_dist, rank_idx, count_lt};
     hipLaunchKernelGGL(vfr::fusion_sweep_kernel, dim3((unsigned)(Nq * plan.chunks)), dim3(64), lds, stq, st, grid, Nq, clip_offsets,
                        moment_offsets, Nv, eps, id_base, level, rk, rows, plan.chunks, plan.per);
     VFR_CHECK_LAUNCH("fusion_sweep_kernel");

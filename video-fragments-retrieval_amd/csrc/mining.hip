@@ -2,7 +2,8 @@
 //
 // The training loss IS the retrieval score: F.pairwise_distance(..., eps).mean() over a span's clips = score(q, video, s, e), the
 // canonical chain of vfr_score_moments_f32 (k-ascending fp32 fma chain over D, IEEE sqrt, sequential fp32 sum s -> e, one IEEE
-// division), restated here so the code objects of score.o do not change.  An item is a training span (query row, own video, s, e):
+// division); its clip distances come from scan_common.h, not from the headers of score.o, so the code objects of score.o do not
+// change.  An item is a training span (query row, own video, s, e):
 //   inter negatives  the span (s, e) applied to every OTHER video of at least e + 1 clips, key = (score bits << 32) | global video
 //   intra negatives  the other moments of the own video (same length, or any but the annotated spans), key = (score bits << 32) |
 //                    global moment id
@@ -16,44 +17,18 @@
 //   mine_intra_kernel  one wave per item, on the shard that holds the own video: lane = clip (its distance into LDS), then lane =
 //                      start clip with a running sum over the end clip, the same list and count; writes the sorted, padded list.
 //   The per-chunk inter lists are merged by vfr_topk_merge_keys (one launch), which also pads with (+inf, -1).
-// The video axis is cut into at most MINE_MAX_CHUNKS chunks, just enough for about MINE_TARGET_WAVES waves: one item against 10 000
-// videos fills the device, 5 000 items run long streams (a running threshold wants them).
-// Workspace: chunks x Nm x h keys, chunks <= MINE_MAX_CHUNKS whatever Nv is.  Nothing is of size Nm x Nv, nothing waits for the host.
-#include "vfr_common.h"
-#include "vfr_math.h"
+// The chunk plan (scan_plan: at most SCAN_MAX_CHUNKS chunks, just enough for about SCAN_TARGET_WAVES waves: one item against 10 000
+// videos fills the device, 5 000 items run long streams -- a running threshold wants them), the list's capacity and sort and the
+// clip-distance helpers are those of scan_common.h.
+// Workspace: chunks x Nm x h keys, chunks <= SCAN_MAX_CHUNKS whatever Nv is.  Nothing is of size Nm x Nv, nothing waits for the host.
+#include "scan_common.h"
 
 namespace vfr {
 namespace {
 
 constexpr int MINE_MAX_CLIPS = 64;                   // as the fused scorer
-constexpr int MINE_MAX_H = 448;
 constexpr int MINE_MAX_X = 8;                        // excluded spans per item
-constexpr int MINE_FAST_D = 100;
-constexpr int MINE_MAX_CHUNKS = 256;
-constexpr int MINE_TARGET_WAVES = 4096;
 constexpr int MINE_INTRA_BUF = 1024;                 // key buffer of the intra scan (>= h + 64)
-constexpr unsigned long long MINE_KEY_MAX = ~0ull;
-constexpr unsigned long long MINE_KEY_EMPTY = 0x7F800000FFFFFFFFull;   // VFR_KEY_EMPTY: an unused slot of a list
-
-// slots of an inter wave's LDS list: a power of two >= h + 64 (a wave appends up to 64 keys before it looks at the fill)
-int mine_cap(int h) { return h == 0 ? 0 : h <= 64 ? 128 : h <= 192 ? 256 : 512; }
-
-struct MinePlan { int chunks; int64_t per; int bound; };
-// chunks = min(ceil(MINE_TARGET_WAVES / Nm), blocks of 64 videos, MINE_MAX_CHUNKS), evened out; `bound` (what the workspace is sized
-// by) does not look at Nv beyond "fewer blocks than that"
-MinePlan mine_plan(int64_t Nm, int64_t Nv)
-{
-    MinePlan p{};
-    const int64_t blocks = cdiv(Nv, 64);
-    int64_t want = cdiv(MINE_TARGET_WAVES, Nm > 0 ? Nm : 1);
-    want = want > MINE_MAX_CHUNKS ? MINE_MAX_CHUNKS : want;
-    int64_t c = want < blocks ? want : blocks;
-    c = c < 1 ? 1 : c;
-    p.bound = (int)c;
-    p.per = cdiv(blocks > 0 ? blocks : 1, c) * 64;
-    p.chunks = (int)cdiv(Nv > 0 ? Nv : 1, p.per);
-    return p;
-}
 
 struct MineItem { int q, gv, s, e, lown, nown; bool wrong; };
 
@@ -75,73 +50,6 @@ __device__ __forceinline__ MineItem mine_item(const int32_t *__restrict__ items,
     return it;
 }
 
-// NC consecutive clip rows against the query row in LDS: NC independent canonical chains (D = 100, 16-byte aligned rows)
-template <int NC>
-__device__ __forceinline__ void mine_dist_fast(const float *__restrict__ vr, const float *qs, float eps, float *out)
-{
-    float acc[NC];
-#pragma unroll
-    for (int i = 0; i < NC; ++i) acc[i] = 0.0f;
-#pragma unroll
-    for (int k4 = 0; k4 < MINE_FAST_D / 4; ++k4) {
-        const float4 y = *reinterpret_cast<const float4 *>(qs + 4 * k4);
-#pragma unroll
-        for (int i = 0; i < NC; ++i) {
-            const float4 x = *reinterpret_cast<const float4 *>(vr + i * MINE_FAST_D + 4 * k4);
-            float t = (x.x - y.x) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
-            t = (x.y - y.y) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
-            t = (x.z - y.z) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
-            t = (x.w - y.w) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NC; ++i) out[i] = __builtin_sqrtf(acc[i]);
-}
-
-// one clip row, any D: qr is the query row in global memory (wave-uniform address)
-__device__ __forceinline__ float mine_dist_any(const float *__restrict__ vr, const float *__restrict__ qr, int D, float eps)
-{
-    float acc = 0.0f;
-    for (int kk = 0; kk < D; ++kk) {
-        const float t = (vr[kk] - qr[kk]) + eps;
-        acc = __builtin_fmaf(t, t, acc);
-    }
-    return __builtin_sqrtf(acc);
-}
-
-// the wave-uniform query row: LDS copy for the fast path, the global row otherwise
-template <bool FAST>
-__device__ __forceinline__ const float *mine_query_row(const float *__restrict__ Q, int q, int D, float *qs, int lane)
-{
-    const float *qg = Q + (int64_t)q * D;
-    if constexpr (FAST) {
-        if (lane < MINE_FAST_D / 4) reinterpret_cast<float4 *>(qs)[lane] = reinterpret_cast<const float4 *>(qg)[lane];
-        __syncthreads();
-        return qs;
-    } else {
-        return qg;
-    }
-}
-
-// bitonic sort of b[0..size) (slots >= cnt filled with KEY_MAX first), one wave
-__device__ __forceinline__ void mine_sort(unsigned long long *b, int cnt, int size, int lane)
-{
-    for (int i = cnt + lane; i < size; i += 64) b[i] = MINE_KEY_MAX;
-    __syncthreads();
-    for (int sz = 2; sz <= size; sz <<= 1)
-        for (int stride = sz >> 1; stride > 0; stride >>= 1) {
-            for (int i = lane; i < size; i += 64) {
-                const int o = i ^ stride;
-                if (o > i) {
-                    const bool asc = (i & sz) == 0;
-                    const unsigned long long x = b[i], y = b[o];
-                    if ((x > y) == asc) { b[i] = y; b[o] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
 // ---- score of named (query, video, span) items: one wave per item ----
 template <bool FAST>
 __global__ __launch_bounds__(64) void mine_spans_kernel(const float *__restrict__ Q, int64_t Nq, const float *__restrict__ V,
@@ -149,7 +57,7 @@ __global__ __launch_bounds__(64) void mine_spans_kernel(const float *__restrict_
                                                         int64_t vid_base, const int32_t *__restrict__ items, int64_t Np,
                                                         float *__restrict__ out, int *__restrict__ bad)
 {
-    __shared__ __attribute__((aligned(16))) float qs[FAST ? MINE_FAST_D + 4 : 4];
+    __shared__ __attribute__((aligned(16))) float qs[FAST ? SCAN_FAST_D + 4 : 4];
     __shared__ float ds[MINE_MAX_CLIPS];
     const int lane = threadIdx.x;
     const int64_t p = blockIdx.x;
@@ -159,13 +67,13 @@ __global__ __launch_bounds__(64) void mine_spans_kernel(const float *__restrict_
         return;
     }
     if (it.lown < 0) return;                                   // another shard's video: untouched
-    const float *qr = mine_query_row<FAST>(Q, it.q, D, qs, lane);
+    const float *qr = query_row<FAST>(Q, it.q, D, qs, lane);
     const int len = it.e - it.s + 1;                           // <= nown <= 64
     if (lane < len) {
         const float *vr = V + (int64_t)(clip_off[it.lown] + it.s + lane) * D;
         float d;
-        if constexpr (FAST) mine_dist_fast<1>(vr, qr, eps, &d);
-        else d = mine_dist_any(vr, qr, D, eps);
+        if constexpr (FAST) clip_dist_fast<1>(vr, qr, eps, &d);
+        else d = clip_dist_any(vr, qr, D, eps);
         ds[lane] = d;
     }
     __syncthreads();
@@ -187,7 +95,7 @@ __global__ __launch_bounds__(64) void mine_inter_kernel(const float *__restrict_
 {
     extern __shared__ __attribute__((aligned(16))) float ssm[];
     float *qs = ssm;                                                                       // [104] (fast path)
-    unsigned long long *buf = reinterpret_cast<unsigned long long *>(ssm + (FAST ? MINE_FAST_D + 4 : 0));   // [cap]
+    unsigned long long *buf = reinterpret_cast<unsigned long long *>(ssm + (FAST ? SCAN_FAST_D + 4 : 0));   // [cap]
     const int lane = threadIdx.x;
     const int64_t m = blockIdx.x / chunks;
     const int ch = (int)(blockIdx.x - m * chunks);
@@ -195,10 +103,10 @@ __global__ __launch_bounds__(64) void mine_inter_kernel(const float *__restrict_
     unsigned long long *out = ws + ((size_t)ch * Nm + m) * h;
     if (it.wrong) {                                            // padding, nothing added
         if (bad && lane == 0 && ch == 0) *bad = 1;
-        for (int i = lane; i < h; i += 64) out[i] = MINE_KEY_EMPTY;
+        for (int i = lane; i < h; i += 64) out[i] = SCAN_KEY_EMPTY;
         return;
     }
-    const float *qr = mine_query_row<FAST>(Q, it.q, D, qs, lane);
+    const float *qr = query_row<FAST>(Q, it.q, D, qs, lane);
     const int s = it.s, e = it.e;
     const int len = e - s < MINE_MAX_CLIPS ? e - s + 1 : MINE_MAX_CLIPS + 1;   // a longer span fits no video (no e - s + 1 overflow)
     const float flen = (float)len;
@@ -207,7 +115,7 @@ __global__ __launch_bounds__(64) void mine_inter_kernel(const float *__restrict_
     const int64_t v0 = (int64_t)ch * per;
     const int64_t v1 = v0 + per < Nv ? v0 + per : Nv;
     const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    unsigned long long thr = MINE_KEY_MAX;                     // keys >= thr cannot be among the chunk's h smallest
+    unsigned long long thr = SCAN_KEY_MAX;                     // keys >= thr cannot be among the chunk's h smallest
     int cnt = 0;                                               // keys in buf (wave-uniform)
     unsigned nlt = 0u;
 
@@ -226,18 +134,18 @@ __global__ __launch_bounds__(64) void mine_inter_kernel(const float *__restrict_
                 if constexpr (FAST) {
                     for (; c + 2 <= len; c += 2) {
                         float d[2];
-                        mine_dist_fast<2>(vr + (int64_t)c * MINE_FAST_D, qr, eps, d);
+                        clip_dist_fast<2>(vr + (int64_t)c * SCAN_FAST_D, qr, eps, d);
                         sum = c == 0 ? d[0] : sum + d[0];
                         sum = sum + d[1];
                     }
                     if (c < len) {
                         float d;
-                        mine_dist_fast<1>(vr + (int64_t)c * MINE_FAST_D, qr, eps, &d);
+                        clip_dist_fast<1>(vr + (int64_t)c * SCAN_FAST_D, qr, eps, &d);
                         sum = c == 0 ? d : sum + d;
                     }
                 } else {
                     for (; c < len; ++c) {
-                        const float d = mine_dist_any(vr + (int64_t)c * D, qr, D, eps);
+                        const float d = clip_dist_any(vr + (int64_t)c * D, qr, D, eps);
                         sum = c == 0 ? d : sum + d;
                     }
                 }
@@ -257,20 +165,20 @@ __global__ __launch_bounds__(64) void mine_inter_kernel(const float *__restrict_
                 cnt += __popcll(mt);
                 if (cnt > cap - 64) {
                     __syncthreads();
-                    mine_sort(buf, cnt, cap, lane);
+                    wave_sort_keys(buf, cnt, cap, lane);
                     if (cnt >= h) { thr = buf[h - 1]; cnt = h; }
                     __syncthreads();
                 }
             }
         }
     }
-    if (h > 0) {
+    if (h > 0) {                                               // the merge sorts: a list of at most h keys goes out as it stands
         __syncthreads();
         if (cnt > h) {
-            mine_sort(buf, cnt, cap, lane);
+            wave_sort_keys(buf, cnt, cap, lane);
             cnt = h;
         }
-        for (int i = lane; i < h; i += 64) out[i] = i < cnt ? buf[i] : MINE_KEY_EMPTY;
+        for (int i = lane; i < h; i += 64) out[i] = i < cnt ? buf[i] : SCAN_KEY_EMPTY;
     }
     if (has_thr && lane == 0 && nlt)
         atomicAdd(reinterpret_cast<unsigned long long *>(count_inter + m), (unsigned long long)nlt);
@@ -287,7 +195,7 @@ __global__ __launch_bounds__(64) void mine_intra_kernel(const float *__restrict_
                                                         int64_t *__restrict__ intra_idx, int64_t *__restrict__ count_intra,
                                                         int *__restrict__ bad)
 {
-    __shared__ __attribute__((aligned(16))) float qs[FAST ? MINE_FAST_D + 4 : 4];
+    __shared__ __attribute__((aligned(16))) float qs[FAST ? SCAN_FAST_D + 4 : 4];
     __shared__ float ds[MINE_MAX_CLIPS];
     __shared__ unsigned long long buf[MINE_INTRA_BUF];
     const int lane = threadIdx.x;
@@ -298,13 +206,13 @@ __global__ __launch_bounds__(64) void mine_intra_kernel(const float *__restrict_
         return;
     }
     if (it.lown < 0) return;                                   // the shard of the own video writes the intra list
-    const float *qr = mine_query_row<FAST>(Q, it.q, D, qs, lane);
+    const float *qr = query_row<FAST>(Q, it.q, D, qs, lane);
     const int n = it.nown, s = it.s, e = it.e;
     if (lane < n) {
         const float *vr = V + (int64_t)(clip_off[it.lown] + lane) * D;
         float d;
-        if constexpr (FAST) mine_dist_fast<1>(vr, qr, eps, &d);
-        else d = mine_dist_any(vr, qr, D, eps);
+        if constexpr (FAST) clip_dist_fast<1>(vr, qr, eps, &d);
+        else d = clip_dist_any(vr, qr, D, eps);
         ds[lane] = d;
     }
     __syncthreads();
@@ -322,7 +230,7 @@ __global__ __launch_bounds__(64) void mine_intra_kernel(const float *__restrict_
     const int64_t mbase = id_base + mom_off[it.lown];
     const int L = e - s, Lmax = any ? n - 1 : L;
     const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    unsigned long long thr = MINE_KEY_MAX;
+    unsigned long long thr = SCAN_KEY_MAX;
     int cnt = 0, nlt = 0;
     float sum = 0.0f;
     for (int Lp = 0; Lp <= Lmax; ++Lp) {                       // lane = start clip s', end clip e' = s' + Lp: the sum runs s' -> e'
@@ -345,7 +253,7 @@ __global__ __launch_bounds__(64) void mine_intra_kernel(const float *__restrict_
                 cnt += __popcll(mt);
                 if (cnt > MINE_INTRA_BUF - 64) {
                     __syncthreads();
-                    mine_sort(buf, cnt, MINE_INTRA_BUF, lane);
+                    wave_sort_keys(buf, cnt, MINE_INTRA_BUF, lane);
                     if (cnt >= h) { thr = buf[h - 1]; cnt = h; }
                     __syncthreads();
                 }
@@ -356,7 +264,7 @@ __global__ __launch_bounds__(64) void mine_intra_kernel(const float *__restrict_
         __syncthreads();
         int size = 64;
         while (size < cnt) size <<= 1;
-        mine_sort(buf, cnt, size, lane);
+        wave_sort_keys(buf, cnt, size, lane);
         cnt = cnt > h ? h : cnt;
         for (int i = lane; i < h; i += 64) {
             const unsigned long long x = i < cnt ? buf[i] : 0ull;
@@ -369,11 +277,6 @@ __global__ __launch_bounds__(64) void mine_intra_kernel(const float *__restrict_
         for (int o = 32; o >= 1; o >>= 1) nlt += __shfl_xor(nlt, o, 64);
         if (lane == 0 && nlt) atomicAdd(reinterpret_cast<unsigned long long *>(count_intra + m), (unsigned long long)nlt);
     }
-}
-
-bool mine_fast(const float *Q, const float *V, int D)
-{
-    return D == MINE_FAST_D && (((uintptr_t)Q) & 15) == 0 && (((uintptr_t)V) & 15) == 0;
 }
 
 }  // namespace
@@ -396,7 +299,7 @@ int vfr_score_spans_f32(const float *Q, int64_t Nq, const float *V, const int32_
     hipStream_t st = vfr::as_stream(stream);
     vfr::ProfScope prof(vfr::SITE_SCORE_OWN, st);
     const dim3 grid((unsigned)Np), block(64);
-    if (vfr::mine_fast(Q, V, D))
+    if (vfr::rows_fast(Q, V, D))
         hipLaunchKernelGGL((vfr::mine_spans_kernel<true>), grid, block, 0, st, Q, Nq, V, clip_offsets, Nv, D, eps, vid_base, items, Np, out,
                            bad);
     else
@@ -408,8 +311,8 @@ int vfr_score_spans_f32(const float *Q, int64_t Nq, const float *V, const int32_
 
 size_t vfr_mine_negatives_workspace_bytes(int64_t Nm, int Nv, int h)
 {
-    if (Nm < 0 || Nv < 0 || h < 0 || h > vfr::MINE_MAX_H || Nm * (int64_t)(h > 0 ? h : 1) > 0x7FFFFFFF) return 0;
-    const vfr::MinePlan p = vfr::mine_plan(Nm, Nv);
+    if (Nm < 0 || Nv < 0 || h < 0 || h > vfr::SCAN_MAX_K || Nm * (int64_t)(h > 0 ? h : 1) > 0x7FFFFFFF) return 0;
+    const vfr::ScanPlan p = vfr::scan_plan(Nm, Nv, vfr::SCAN_TARGET_WAVES);
     return vfr::align_up((size_t)p.bound * (size_t)Nm * (size_t)h * 8 + 256, 256);
 }
 
@@ -420,7 +323,7 @@ int vfr_mine_negatives_f32(const float *Q, int64_t Nq, const float *V, const int
                            int64_t *intra_idx, int64_t *count_inter, int64_t *count_intra, int *bad, void *workspace,
                            size_t workspace_bytes, vfr_stream_t stream)
 {
-    VFR_REQUIRE(Nq >= 0 && Nm >= 0 && Nv >= 0 && total_clips >= 0 && D > 0 && h >= 0 && h <= vfr::MINE_MAX_H && max_clips >= 0 &&
+    VFR_REQUIRE(Nq >= 0 && Nm >= 0 && Nv >= 0 && total_clips >= 0 && D > 0 && h >= 0 && h <= vfr::SCAN_MAX_K && max_clips >= 0 &&
                 max_clips <= vfr::MINE_MAX_CLIPS && id_base >= 0 && vid_base >= 0, VFR_EINVAL,
                 "vfr_mine_negatives_f32: bad shape (h <= 448, max_clips <= 64, sizes, id_base, vid_base >= 0)");
     VFR_REQUIRE(intra_mode == VFR_MINE_SAME_LENGTH || intra_mode == VFR_MINE_ANY, VFR_EINVAL,
@@ -439,14 +342,14 @@ int vfr_mine_negatives_f32(const float *Q, int64_t Nq, const float *V, const int
     VFR_REQUIRE(intra_mode != VFR_MINE_ANY || X == 0 || Nm == 0 || excl, VFR_EINVAL, "vfr_mine_negatives_f32: excl is null with X > 0");
     VFR_REQUIRE(Nv == 0 || (clip_offsets && moment_offsets && (V || total_clips == 0)), VFR_EINVAL,
                 "vfr_mine_negatives_f32: null clip bank");
-    const vfr::MinePlan plan = vfr::mine_plan(Nm, Nv);
+    const vfr::ScanPlan plan = vfr::scan_plan(Nm, Nv, vfr::SCAN_TARGET_WAVES);
     VFR_REQUIRE(Nm * plan.chunks <= 0x7FFFFFFF, VFR_EINVAL, "vfr_mine_negatives_f32: too many (item, chunk) waves");
     const size_t need = vfr_mine_negatives_workspace_bytes(Nm, Nv, h);
     VFR_REQUIRE(workspace && workspace_bytes >= need, VFR_EWORKSPACE, "vfr_mine_negatives_f32: workspace %zu < %zu bytes",
                 workspace_bytes, need);
     if (Nm == 0) return VFR_OK;
     hipStream_t st = vfr::as_stream(stream);
-    const bool fast = vfr::mine_fast(Q, V, D);
+    const bool fast = vfr::rows_fast(Q, V, D);
     const bool inter_lists = h > 0 && inter_dist != nullptr, intra_lists = h > 0 && intra_dist != nullptr;
     unsigned long long *keys = static_cast<unsigned long long *>(workspace);
     if (intra_lists || count_intra || (bad && !inter_lists && !count_inter)) {
@@ -465,8 +368,8 @@ int vfr_mine_negatives_f32(const float *Q, int64_t Nq, const float *V, const int
     if (inter_lists || count_inter) {
         vfr::ProfScope prof(vfr::SITE_SCORE_PAIRS, st);
         const int hh = inter_lists ? h : 0;
-        const int cap = vfr::mine_cap(hh);
-        const size_t lds = (fast ? (size_t)(vfr::MINE_FAST_D + 4) * 4 : 0) + (size_t)cap * 8;
+        const int cap = vfr::scan_cap(hh);
+        const size_t lds = (fast ? (size_t)(vfr::SCAN_FAST_D + 4) * 4 : 0) + (size_t)cap * 8;
         const dim3 grid((unsigned)(Nm * plan.chunks)), block(64);
         if (fast)
             hipLaunchKernelGGL((vfr::mine_inter_kernel<true>), grid, block, lds, st, Q, Nq, V, clip_offsets, Nv, D, eps, vid_base, items,

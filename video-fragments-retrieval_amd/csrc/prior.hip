@@ -3,8 +3,8 @@
 // A moment table T gives every (clip count n, local moment j in utils.generate_moments order) one fp32 entry: a finite bias >= 0 or
 // +inf = excluded.  table_off [max_clips + 2] = prefix sums of n (n + 1) / 2, table [table_off[max_clips + 1]].  The ranking key
 // changes at the MOMENT: score(q, v, j) is the canonical chain of vfr_score_moments_f32 (k-ascending fp32 fma chain of
-// ((v - q) + eps)^2, IEEE sqrt, sequential fp32 sum s -> e, one IEEE division), restated here so the code objects of score.o do not
-// change, and
+// ((v - q) + eps)^2, IEEE sqrt, sequential fp32 sum s -> e, one IEEE division); its clip distances come from scan_common.h, not
+// from the headers of score.o, so the code objects of score.o do not change, and
 //     g(q, v, j) = fl(score(q, v, j) + T[n_v][j])                       (__fadd_rn: one rounded addition, contracted with nothing)
 // is what the key carries: key = (bits of g << 32) | (id_base + moment_offsets[v] + j).  A moment is a candidate iff g < +inf; an
 // entry that is NaN or < 0 sets *bad and excludes its moment.  A table of zeros gives the bits of vfr_score_topk_f32 /
@@ -23,51 +23,15 @@
 //                      nor counted) are collected under a running threshold into an LDS list of 128 / 256 / 512 keys that is sorted and
 //                      cut back to k when it fills; the chunk's list goes to ws[chunk][query][0..k).
 //   The per-chunk lists are merged by vfr_topk_merge_keys (one launch), which also pads with (+inf, -1).
-// The chunk plan is the one of fusion.hip / mining.hip: at most PRI_MAX_CHUNKS chunks, just enough for about PRI_TARGET_WAVES waves.
+// The chunk plan, the list's capacity and sort, the rank-key counters and the clip-distance helpers are those of scan_common.h.
 // LDS of a scan wave = 416 (FAST: the query row) + 256 max(max_clips, 1) + 8 slots(k) bytes <= 416 + 16 384 + 4 096.
-// Workspace: chunks x Nq x k keys, chunks <= PRI_MAX_CHUNKS whatever Nv is.  Nothing is of size Nq x Nv, nothing waits for the host.
-#include "vfr_common.h"
-#include "vfr_math.h"
+// Workspace: chunks x Nq x k keys, chunks <= SCAN_MAX_CHUNKS whatever Nv is.  Nothing is of size Nq x Nv, nothing waits for the host.
+#include "scan_common.h"
 
 namespace vfr {
 namespace {
 
 constexpr int PRI_MAX_CLIPS = 64;                    // as the fused scorer
-constexpr int PRI_MAX_K = 448;
-constexpr int PRI_MAX_RANK = 4;
-constexpr int PRI_FAST_D = 100;
-constexpr int PRI_MAX_CHUNKS = 256;
-constexpr int PRI_TARGET_WAVES = 4096;
-constexpr unsigned long long PRI_KEY_MAX = ~0ull;
-constexpr unsigned long long PRI_KEY_EMPTY = 0x7F800000FFFFFFFFull;   // VFR_KEY_EMPTY: an unused slot of a list; no candidate reaches it
-
-// slots of a scan wave's LDS list: a power of two >= k + 64 (a wave appends up to 64 keys before it looks at the fill)
-int pri_cap(int k) { return k == 0 ? 0 : k <= 64 ? 128 : k <= 192 ? 256 : 512; }
-
-struct PriPlan { int chunks; int64_t per; int bound; };
-// chunks = min(ceil(PRI_TARGET_WAVES / Nq), blocks of 64 videos, PRI_MAX_CHUNKS), evened out; `bound` (what the workspace is sized
-// by) does not look at Nv beyond "fewer blocks than that"
-PriPlan pri_plan(int64_t Nq, int64_t Nv)
-{
-    PriPlan p{};
-    const int64_t blocks = cdiv(Nv, 64);
-    int64_t want = cdiv(PRI_TARGET_WAVES, Nq > 0 ? Nq : 1);
-    want = want > PRI_MAX_CHUNKS ? PRI_MAX_CHUNKS : want;
-    int64_t c = want < blocks ? want : blocks;
-    c = c < 1 ? 1 : c;
-    p.bound = (int)c;
-    p.per = cdiv(blocks > 0 ? blocks : 1, c) * 64;
-    p.chunks = (int)cdiv(Nv > 0 ? Nv : 1, p.per);
-    return p;
-}
-
-struct PriRank {
-    int num_rank;
-    const float *dist;           // [num_rank, Nq]
-    const int64_t *idx;
-    int64_t *count_lt;
-};
-
 struct PriTable {
     const int32_t *off;          // [max_clips + 2]
     const float *val;            // [len]
@@ -75,78 +39,6 @@ struct PriTable {
     int max_clips;
     int *bad;                    // nullable
 };
-
-// NC consecutive clip rows against the query row in LDS: NC independent canonical chains (D = 100, 16-byte aligned rows)
-template <int NC>
-__device__ __forceinline__ void pri_dist_fast(const float *__restrict__ vr, const float *qs, float eps, float *out)
-{
-    float acc[NC];
-#pragma unroll
-    for (int i = 0; i < NC; ++i) acc[i] = 0.0f;
-#pragma unroll
-    for (int k4 = 0; k4 < PRI_FAST_D / 4; ++k4) {
-        const float4 y = *reinterpret_cast<const float4 *>(qs + 4 * k4);
-#pragma unroll
-        for (int i = 0; i < NC; ++i) {
-            const float4 x = *reinterpret_cast<const float4 *>(vr + i * PRI_FAST_D + 4 * k4);
-            float t = (x.x - y.x) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
-            t = (x.y - y.y) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
-            t = (x.z - y.z) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
-            t = (x.w - y.w) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NC; ++i) out[i] = __builtin_sqrtf(acc[i]);
-}
-
-// one clip row, any D: qr is the query row in global memory (wave-uniform address)
-__device__ __forceinline__ float pri_dist_any(const float *__restrict__ vr, const float *__restrict__ qr, int D, float eps)
-{
-    float acc = 0.0f;
-    for (int kk = 0; kk < D; ++kk) {
-        const float t = (vr[kk] - qr[kk]) + eps;
-        acc = __builtin_fmaf(t, t, acc);
-    }
-    return __builtin_sqrtf(acc);
-}
-
-// the wave-uniform query row: LDS copy for the fast path, the global row otherwise
-template <bool FAST>
-__device__ __forceinline__ const float *pri_query_row(const float *__restrict__ Q, int64_t q, int D, float *qs, int lane)
-{
-    const float *qg = Q + q * D;
-    if constexpr (FAST) {
-        if (lane < PRI_FAST_D / 4) reinterpret_cast<float4 *>(qs)[lane] = reinterpret_cast<const float4 *>(qg)[lane];
-        __syncthreads();
-        return qs;
-    } else {
-        return qg;
-    }
-}
-
-// distances of the n clips from row c0 on, into dst[c * stride]
-template <bool FAST>
-__device__ __forceinline__ void pri_clips(const float *__restrict__ V, int64_t c0, int n, const float *qr, int D, float eps, float *dst,
-                                          int stride)
-{
-    if constexpr (FAST) {
-        const float *vr = V + c0 * PRI_FAST_D;
-        int c = 0;
-        for (; c + 2 <= n; c += 2) {
-            float d[2];
-            pri_dist_fast<2>(vr + (int64_t)c * PRI_FAST_D, qr, eps, d);
-            dst[c * stride] = d[0];
-            dst[(c + 1) * stride] = d[1];
-        }
-        if (c < n) {
-            float d;
-            pri_dist_fast<1>(vr + (int64_t)c * PRI_FAST_D, qr, eps, &d);
-            dst[c * stride] = d;
-        }
-    } else {
-        for (int c = 0; c < n; ++c) dst[c * stride] = pri_dist_any(V + (c0 + c) * D, qr, D, eps);
-    }
-}
 
 // the table row of an n-clip video (n <= max_clips, so table_off[n] exists); a row that would leave the table is refused: the video
 // then has no candidate at all
@@ -171,32 +63,13 @@ __device__ __forceinline__ float pri_biased(float sc, float b, bool &wrong)
     return __fadd_rn(sc, b);
 }
 
-// bitonic sort of b[0..size) (slots >= cnt filled with KEY_MAX first), one wave; size a power of two >= cnt
-__device__ __forceinline__ void pri_sort(unsigned long long *b, int cnt, int size, int lane)
-{
-    for (int i = cnt + lane; i < size; i += 64) b[i] = PRI_KEY_MAX;
-    __syncthreads();
-    for (int sz = 2; sz <= size; sz <<= 1)
-        for (int stride = sz >> 1; stride > 0; stride >>= 1) {
-            for (int i = lane; i < size; i += 64) {
-                const int o = i ^ stride;
-                if (o > i) {
-                    const bool asc = (i & sz) == 0;
-                    const unsigned long long x = b[i], y = b[o];
-                    if ((x > y) == asc) { b[i] = y; b[o] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
 // ---- each query against ONE video own[q]: one wave per query; lane = clip, then lane = start clip ----
 template <bool FAST>
 __global__ __launch_bounds__(64) void prior_own_kernel(const float *__restrict__ Q, int64_t Nq, const float *__restrict__ V,
                                                        const int32_t *__restrict__ clip_off, const int32_t *__restrict__ own, int Nv,
                                                        int D, float eps, int Mmax, const PriTable tb, float *__restrict__ scores)
 {
-    __shared__ __attribute__((aligned(16))) float qs[FAST ? PRI_FAST_D + 4 : 4];
+    __shared__ __attribute__((aligned(16))) float qs[FAST ? SCAN_FAST_D + 4 : 4];
     __shared__ float ds[PRI_MAX_CLIPS];
     const int lane = threadIdx.x;
     const int64_t q = blockIdx.x;
@@ -214,8 +87,8 @@ __global__ __launch_bounds__(64) void prior_own_kernel(const float *__restrict__
     if (row == nullptr) n = 0;
     const int M = n * (n + 1) / 2;                             // <= Mmax: Mmax >= max_clips (max_clips + 1) / 2
     for (int m = M + lane; m < Mmax; m += 64) out[m] = __builtin_inff();      // slots past this video's moments
-    const float *qr = pri_query_row<FAST>(Q, q, D, qs, lane);
-    if (lane < n) pri_clips<FAST>(V, c0 + lane, 1, qr, D, eps, ds + lane, 1);
+    const float *qr = query_row<FAST>(Q, q, D, qs, lane);
+    if (lane < n) clip_dists<FAST>(V, c0 + lane, 1, qr, D, eps, ds + lane, 1);
     __syncthreads();
     if (lane < n) {
         float sum = 0.0f;
@@ -234,31 +107,30 @@ template <bool FAST>
 __global__ __launch_bounds__(64) void prior_scan_kernel(const float *__restrict__ Q, int64_t Nq, const float *__restrict__ V,
                                                         const int32_t *__restrict__ clip_off, const int64_t *__restrict__ mom_off,
                                                         int Nv, int D, float eps, int64_t id_base, int level, int k, int cap,
-                                                        PriRank rk, int ds_rows, int chunks, int64_t per, const PriTable tb,
+                                                        ScanRank rk, int ds_rows, int chunks, int64_t per, const PriTable tb,
                                                         unsigned long long *__restrict__ ws)
 {
     extern __shared__ __attribute__((aligned(16))) float ssm[];
     float *qs = ssm;                                                                        // [104] (fast path)
-    float *ds = ssm + (FAST ? PRI_FAST_D + 4 : 0);                                          // [ds_rows][64] clip distances, lane-minor
+    float *ds = ssm + (FAST ? SCAN_FAST_D + 4 : 0);                                          // [ds_rows][64] clip distances, lane-minor
     unsigned long long *buf = reinterpret_cast<unsigned long long *>(ds + (size_t)ds_rows * 64);   // [cap]
     const int lane = threadIdx.x;
     const int64_t q = blockIdx.x / chunks;
     const int ch = (int)(blockIdx.x - q * chunks);
-    const float *qr = pri_query_row<FAST>(Q, q, D, qs, lane);
+    const float *qr = query_row<FAST>(Q, q, D, qs, lane);
 
-    unsigned long long rkey[PRI_MAX_RANK];
+    unsigned long long rkey[SCAN_MAX_RANK];
 #pragma unroll
-    for (int r = 0; r < PRI_MAX_RANK; ++r)
+    for (int r = 0; r < SCAN_MAX_RANK; ++r)
         rkey[r] = r < rk.num_rank ? make_key(rk.dist[r * Nq + q], (unsigned)rk.idx[r * Nq + q]) : 0ull;
-    int nlt[PRI_MAX_RANK] = {0, 0, 0, 0};
+    int nlt[SCAN_MAX_RANK] = {0, 0, 0, 0};
 
     const int64_t v0 = (int64_t)ch * per;
     const int64_t v1 = v0 + per < Nv ? v0 + per : Nv;
-    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     const float inf = __builtin_inff();
-    unsigned long long thr = PRI_KEY_MAX;                      // keys >= thr cannot be among the chunk's k smallest
+    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    unsigned long long thr = SCAN_KEY_MAX;                     // keys >= thr cannot be among the chunk's k smallest
     int cnt = 0;                                               // keys in buf (wave-uniform)
-    bool wrong = false;
     // a wave-uniform append of the lanes' keys under the threshold; the list is sorted and cut back to k when it may overflow
     auto append = [&](bool take, unsigned long long key) {
         const unsigned long long mt = __ballot(take);
@@ -267,12 +139,13 @@ __global__ __launch_bounds__(64) void prior_scan_kernel(const float *__restrict_
             cnt += __popcll(mt);
             if (cnt > cap - 64) {
                 __syncthreads();
-                pri_sort(buf, cnt, cap, lane);
+                wave_sort_keys(buf, cnt, cap, lane);
                 if (cnt >= k) { thr = buf[k - 1]; cnt = k; }
                 __syncthreads();
             }
         }
     };
+    bool wrong = false;
 
     for (int64_t vb = v0; vb < v1; vb += 64) {
         const int64_t l = vb + lane;
@@ -286,10 +159,10 @@ __global__ __launch_bounds__(64) void prior_scan_kernel(const float *__restrict_
             row = pri_row(tb, n, wrong);
             if (row == nullptr) n = 0;
             mbase = id_base + mom_off[l];
-            pri_clips<FAST>(V, (int64_t)c0, n, qr, D, eps, ds + lane, 64);                  // the lane's own column
+            clip_dists<FAST>(V, (int64_t)c0, n, qr, D, eps, ds + lane, 64);                  // the lane's own column
         }
         if (level == VFR_PRIOR_VIDEOS) {
-            unsigned long long best = PRI_KEY_EMPTY;
+            unsigned long long best = SCAN_KEY_EMPTY;
             for (int s = 0; s < n; ++s) {
                 float sum = 0.0f;
                 const int jrow = n + (s * (2 * n - s - 1)) / 2 - s - 1;               // moment_index(n, s, e) = jrow + e for e > s
@@ -304,11 +177,8 @@ __global__ __launch_bounds__(64) void prior_scan_kernel(const float *__restrict_
                     }
                 }
             }
-            const bool has = best != PRI_KEY_EMPTY;            // a video without a candidate is neither counted nor listed
-            if (has) {
-#pragma unroll
-                for (int r = 0; r < PRI_MAX_RANK; ++r) nlt[r] += (r < rk.num_rank && best < rkey[r]) ? 1 : 0;
-            }
+            const bool has = best != SCAN_KEY_EMPTY;            // a video without a candidate is neither counted nor listed
+            if (has) scan_rank_count(rk.num_rank, rkey, best, nlt);
             if (k > 0) append(has && best < thr, best);
         } else {
             // the wave-uniform loop over the widest triangle of the block: a lane past its own video's end takes no part
@@ -326,10 +196,7 @@ __global__ __launch_bounds__(64) void prior_scan_kernel(const float *__restrict_
                     const float g = live ? pri_biased(sum / (float)(e2 - s + 1), row[j], wrong) : inf;
                     const bool cand = g < inf;                 // excluded moments stop here: no key, no count, no insert
                     const unsigned long long key = make_key(g, (unsigned)(mbase + j));
-                    if (cand) {
-#pragma unroll
-                        for (int r = 0; r < PRI_MAX_RANK; ++r) nlt[r] += (r < rk.num_rank && key < rkey[r]) ? 1 : 0;
-                    }
+                    if (cand) scan_rank_count(rk.num_rank, rkey, key, nlt);
                     if (k > 0) append(cand && key < thr, key);
                 }
             }
@@ -339,14 +206,14 @@ __global__ __launch_bounds__(64) void prior_scan_kernel(const float *__restrict_
         __syncthreads();
         int size = 64;
         while (size < cnt) size <<= 1;                         // cnt <= cap, a power of two
-        pri_sort(buf, cnt, size, lane);
+        wave_sort_keys(buf, cnt, size, lane);
         cnt = cnt > k ? k : cnt;
         unsigned long long *out = ws + ((size_t)ch * Nq + q) * k;
-        for (int i = lane; i < k; i += 64) out[i] = i < cnt ? buf[i] : PRI_KEY_EMPTY;
+        for (int i = lane; i < k; i += 64) out[i] = i < cnt ? buf[i] : SCAN_KEY_EMPTY;
     }
     if (rk.num_rank > 0) {
 #pragma unroll
-        for (int r = 0; r < PRI_MAX_RANK; ++r) {
+        for (int r = 0; r < SCAN_MAX_RANK; ++r) {
             // a lane counts at most its share of the 2^32 ids, the wave's sum needs 64 bits (one wave may stream the whole bank)
             unsigned long long x = (unsigned long long)(unsigned)nlt[r];
 #pragma unroll
@@ -356,11 +223,6 @@ __global__ __launch_bounds__(64) void prior_scan_kernel(const float *__restrict_
         }
     }
     if (tb.bad && wrong) *tb.bad = 1;
-}
-
-bool pri_fast(const float *Q, const float *V, int D)
-{
-    return D == PRI_FAST_D && (((uintptr_t)Q) & 15) == 0 && (((uintptr_t)V) & 15) == 0;
 }
 
 PriTable pri_table(const int32_t *table_off, const float *table, int max_clips, int *bad)
@@ -390,7 +252,7 @@ int vfr_score_prior_own_f32(const float *Q, int64_t Nq, const float *V, const in
     vfr::ProfScope prof(vfr::SITE_SCORE_OWN, st);
     const vfr::PriTable tb = vfr::pri_table(table_off, table, max_clips, bad);
     const dim3 grid((unsigned)Nq), block(64);
-    if (vfr::pri_fast(Q, V, D))
+    if (vfr::rows_fast(Q, V, D))
         hipLaunchKernelGGL((vfr::prior_own_kernel<true>), grid, block, 0, st, Q, Nq, V, clip_offsets, own, Nv, D, eps, Mmax, tb, scores);
     else
         hipLaunchKernelGGL((vfr::prior_own_kernel<false>), grid, block, 0, st, Q, Nq, V, clip_offsets, own, Nv, D, eps, Mmax, tb, scores);
@@ -400,8 +262,8 @@ int vfr_score_prior_own_f32(const float *Q, int64_t Nq, const float *V, const in
 
 size_t vfr_score_prior_workspace_bytes(int64_t Nq, int Nv, int k)
 {
-    if (Nq < 0 || Nv < 0 || k < 0 || k > vfr::PRI_MAX_K || Nq * (int64_t)(k > 0 ? k : 1) > 0x7FFFFFFF) return 0;
-    const vfr::PriPlan p = vfr::pri_plan(Nq, Nv);
+    if (Nq < 0 || Nv < 0 || k < 0 || k > vfr::SCAN_MAX_K || Nq * (int64_t)(k > 0 ? k : 1) > 0x7FFFFFFF) return 0;
+    const vfr::ScanPlan p = vfr::scan_plan(Nq, Nv, vfr::SCAN_TARGET_WAVES);
     return vfr::align_up((size_t)p.bound * (size_t)Nq * (size_t)k * 8 + 256, 256);
 }
 
@@ -414,13 +276,13 @@ int vfr_score_prior_f32(const float *Q, int64_t Nq, const float *V, const int32_
     (void)min_clips;
     VFR_REQUIRE(level == VFR_PRIOR_MOMENTS || level == VFR_PRIOR_VIDEOS, VFR_EINVAL,
                 "vfr_score_prior_f32: level %d (0 = moments, 1 = videos)", level);
-    VFR_REQUIRE(Nq >= 0 && Nv >= 0 && total_clips >= 0 && D > 0 && k >= 0 && k <= vfr::PRI_MAX_K && max_clips >= 0 &&
+    VFR_REQUIRE(Nq >= 0 && Nv >= 0 && total_clips >= 0 && D > 0 && k >= 0 && k <= vfr::SCAN_MAX_K && max_clips >= 0 &&
                 max_clips <= vfr::PRI_MAX_CLIPS && id_base >= 0, VFR_EINVAL,
                 "vfr_score_prior_f32: bad shape (k <= 448, max_clips <= 64, D >= 1, sizes, id_base >= 0)");
     VFR_REQUIRE(id_base + (int64_t)total_clips * (max_clips + 1) / 2 <= (int64_t(1) << 32), VFR_EINVAL,
                 "vfr_score_prior_f32: id_base + moments must stay below 2^32");
     VFR_REQUIRE(Nq * (int64_t)(k > 0 ? k : 1) <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_prior_f32: Nq * k must stay below 2^31");
-    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::PRI_MAX_RANK, VFR_EINVAL, "vfr_score_prior_f32: num_rank %d (0 .. 4)", num_rank);
+    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::SCAN_MAX_RANK, VFR_EINVAL, "vfr_score_prior_f32: num_rank %d (0 .. 4)", num_rank);
     VFR_REQUIRE(num_rank == 0 || (rank_dist && rank_idx && count_lt), VFR_EINVAL,
                 "vfr_score_prior_f32: num_rank > 0 needs rank_dist, rank_idx and count_lt");
     VFR_REQUIRE(k == 0 || Nq == 0 || (out_dist && out_idx), VFR_EINVAL, "vfr_score_prior_f32: k > 0 needs out_dist / out_idx");
@@ -428,7 +290,7 @@ int vfr_score_prior_f32(const float *Q, int64_t Nq, const float *V, const int32_
     VFR_REQUIRE(Nv == 0 || (clip_offsets && moment_offsets && (V || total_clips == 0)), VFR_EINVAL,
                 "vfr_score_prior_f32: null clip bank (V, clip_offsets, moment_offsets)");
     VFR_REQUIRE(Nv == 0 || max_clips == 0 || (table_off && table), VFR_EINVAL, "vfr_score_prior_f32: null table_off / table");
-    const vfr::PriPlan plan = vfr::pri_plan(Nq, Nv);
+    const vfr::ScanPlan plan = vfr::scan_plan(Nq, Nv, vfr::SCAN_TARGET_WAVES);
     VFR_REQUIRE(Nq * plan.chunks <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_prior_f32: too many (query, chunk) waves");
     const size_t need = vfr_score_prior_workspace_bytes(Nq, Nv, k);
     VFR_REQUIRE(workspace && workspace_bytes >= need, VFR_EWORKSPACE, "vfr_score_prior_f32: workspace %zu < %zu bytes", workspace_bytes,
@@ -438,11 +300,11 @@ int vfr_score_prior_f32(const float *Q, int64_t Nq, const float *V, const int32_
     unsigned long long *keys = static_cast<unsigned long long *>(workspace);
     {
         vfr::ProfScope prof(vfr::SITE_SCORE_PAIRS, st);
-        const bool fast = vfr::pri_fast(Q, V, D);
+        const bool fast = vfr::rows_fast(Q, V, D);
         const int rows = max_clips < 1 ? 1 : max_clips;
-        const int cap = vfr::pri_cap(k);
-        const size_t lds = (fast ? (size_t)(vfr::PRI_FAST_D + 4) * 4 : 0) + (size_t)rows * 64 * 4 + (size_t)cap * 8;   // <= 416 + 16 K + 4 K
-        const vfr::PriRank rk{num_rank, rank_dist, rank_idx, count_lt};
+        const int cap = vfr::scan_cap(k);
+        const size_t lds = (fast ? (size_t)(vfr::SCAN_FAST_D + 4) * 4 : 0) + (size_t)rows * 64 * 4 + (size_t)cap * 8;   // <= 416 + 16 K + 4 K
+        const vfr::ScanRank rk{num_rank, rank_dist, rank_idx, count_lt};
         const vfr::PriTable tb = vfr::pri_table(table_off, table, max_clips, bad);
         const dim3 grid((unsigned)(Nq * plan.chunks)), block(64);
         if (fast)

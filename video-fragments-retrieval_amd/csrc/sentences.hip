@@ -2,8 +2,8 @@
 //
 // The reverse direction of the scorers of score.hip / subset.hip: the PROBE (video, start clip, end clip) owns the list and the
 // sentences of the bank are ranked.  score(m, j) is the canonical chain of vfr_score_moments_f32 (k-ascending fp32 fma chain over
-// D, sequential fp32 sum over the span, one IEEE division), restated here so the code objects of score.o do not change;
-// key = (fp32 bits of the score << 32) | (sent_base + j), order ascending.
+// D, sequential fp32 sum over the span, one IEEE division), written out here (not taken from the headers of score.o, so its code
+// objects do not change); key = (fp32 bits of the score << 32) | (sent_base + j), order ascending.
 //
 // Kernel (a translation unit of its own):
 //   sentences_scan_kernel  one wave per (tile of SEN_P consecutive probes, chunk of the sentence axis).  lane = sentence: its row
@@ -17,74 +17,44 @@
 //                          and the k smallest keys collected under a running threshold into a per-probe LDS list that is
 //                          sorted and cut back to k when it fills; the chunk's list goes to ws[chunk][probe][0..k).
 //   The per-chunk lists are merged by vfr_topk_merge_keys (one launch), which also pads with (+inf, -1).
-// The sentence axis is cut into at most SEN_MAX_CHUNKS chunks, just enough for about SEN_TARGET_WAVES waves: one probe against
-// 33 000 sentences fills the device, 5 000 probes run long streams (a running threshold wants them).
-// Workspace: chunks x Nm x k keys, chunks <= SEN_MAX_CHUNKS whatever Ns is.  Nothing is of size Nm x Ns, nothing waits for the host.
-#include "vfr_common.h"
-#include "vfr_math.h"
+// The chunk plan is scan_plan of scan_common.h over probe tiles: at most SCAN_MAX_CHUNKS chunks of the sentence axis, just enough for
+// about SEN_TARGET_WAVES waves: one probe against 33 000 sentences fills the device, 5 000 probes run long streams (a running
+// threshold wants them).  The list capacity, the key constants and the sort inside `compact` are the shared ones as well; the
+// per-probe list state lives in LDS (SenTile), so the append stays here.
+// Workspace: chunks x Nm x k keys, chunks <= SCAN_MAX_CHUNKS whatever Ns is.  Nothing is of size Nm x Ns, nothing waits for the host.
+#include "scan_common.h"
 
 namespace vfr {
 namespace {
 
 constexpr int SEN_P = 8;                            // probes per tile
 constexpr int SEN_MAX_CLIPS = 64;                   // as the fused scorer
-constexpr int SEN_MAX_K = 448;
-constexpr int SEN_MAX_RANK = 4;
-constexpr int SEN_FAST_D = 100;
-constexpr int SEN_MAX_CHUNKS = 256;
 constexpr int SEN_TARGET_WAVES = 2048;
-constexpr unsigned long long SEN_KEY_MAX = ~0ull;
-constexpr unsigned long long SEN_KEY_EMPTY = 0x7F800000FFFFFFFFull;   // VFR_KEY_EMPTY: an unused slot of a list
 
-// slots of a probe's LDS list: a power of two >= k + 64 (a wave appends up to 64 keys before it looks at the fill)
-int sen_cap(int k) { return k == 0 ? 0 : k <= 64 ? 128 : k <= 192 ? 256 : 512; }
-
-struct SenPlan { int64_t tiles; int chunks; int64_t per; int bound; };
-// chunks = min(ceil(SEN_TARGET_WAVES / tiles), blocks of 64 sentences, SEN_MAX_CHUNKS), evened out; `bound` (what the workspace
-// is sized by) does not look at Ns beyond "fewer blocks than that"
-SenPlan sen_plan(int64_t Nm, int64_t Ns)
-{
-    SenPlan p{};
-    p.tiles = cdiv(Nm, SEN_P);
-    const int64_t blocks = cdiv(Ns, 64);
-    int64_t want = cdiv(SEN_TARGET_WAVES, p.tiles > 0 ? p.tiles : 1);
-    want = want > SEN_MAX_CHUNKS ? SEN_MAX_CHUNKS : want;
-    int64_t c = want < blocks ? want : blocks;
-    c = c < 1 ? 1 : c;
-    p.bound = (int)c;
-    p.per = cdiv(blocks > 0 ? blocks : 1, c) * 64;
-    p.chunks = (int)cdiv(Ns > 0 ? Ns : 1, p.per);
-    return p;
-}
-
-struct SenRank {
-    int num_rank;
-    const float *dist;        // [num_rank, Nm]
-    const int64_t *idx;
-    int64_t *count_lt;
-};
+// probe tiles = the waves of a pass without chunks: what scan_plan spreads over the sentence axis
+int64_t sen_tiles(int64_t Nm) { return cdiv(Nm, SEN_P); }
 
 struct SenTile {              // the tile's probes (lv < 0: nothing to score) and their running state
     int lv[SEN_P], s[SEN_P], e[SEN_P], c0[SEN_P], cnt[SEN_P];
-    unsigned nlt[SEN_P][SEN_MAX_RANK];
+    unsigned nlt[SEN_P][SCAN_MAX_RANK];
     unsigned long long thr[SEN_P];
-    unsigned long long rkey[SEN_P][SEN_MAX_RANK];
+    unsigned long long rkey[SEN_P][SCAN_MAX_RANK];
 };
 
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
 // NC clips against the lane's sentence row x: NC independent canonical chains, clip rows wave-uniform
 template <int NC>
-__device__ __forceinline__ void sen_dist_fast(const float4 (&x)[SEN_FAST_D / 4], const float *__restrict__ vb, float eps, float *out)
+__device__ __forceinline__ void sen_dist_fast(const float4 (&x)[SCAN_FAST_D / 4], const float *__restrict__ vb, float eps, float *out)
 {
     float acc[NC];
 #pragma unroll
     for (int i = 0; i < NC; ++i) acc[i] = 0.0f;
 #pragma unroll
-    for (int k4 = 0; k4 < SEN_FAST_D / 4; ++k4) {
+    for (int k4 = 0; k4 < SCAN_FAST_D / 4; ++k4) {
 #pragma unroll
         for (int i = 0; i < NC; ++i) {
-            const float4 y = *reinterpret_cast<const float4 *>(vb + i * SEN_FAST_D + 4 * k4);
+            const float4 y = *reinterpret_cast<const float4 *>(vb + i * SCAN_FAST_D + 4 * k4);
             float t = (y.x - x[k4].x) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
             t = (y.y - x[k4].y) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
             t = (y.z - x[k4].z) + eps; acc[i] = __builtin_fmaf(t, t, acc[i]);
@@ -101,7 +71,7 @@ template <bool FAST>
 __global__ __launch_bounds__(64) void sentences_scan_kernel(const float *__restrict__ S, int64_t Ns, const float *__restrict__ V,
                                                             const int32_t *__restrict__ clip_off, int Nv, int D, float eps,
                                                             const int32_t *__restrict__ probes, int64_t Nm, int64_t vid_base,
-                                                            int64_t sent_base, int k, int cap, SenRank rk, int rows, int chunks,
+                                                            int64_t sent_base, int k, int cap, ScanRank rk, int rows, int chunks,
                                                             int64_t per, int *__restrict__ bad, unsigned long long *__restrict__ ws)
 {
     extern __shared__ __attribute__((aligned(16))) float ssm[];
@@ -132,9 +102,9 @@ __global__ __launch_bounds__(64) void sentences_scan_kernel(const float *__restr
             if (wrong && bad) *bad = 1;
         }
         T.lv[lane] = lv; T.s[lane] = s; T.e[lane] = e; T.c0[lane] = c0; T.cnt[lane] = 0;
-        T.thr[lane] = SEN_KEY_MAX;
+        T.thr[lane] = SCAN_KEY_MAX;
 #pragma unroll
-        for (int r = 0; r < SEN_MAX_RANK; ++r) {
+        for (int r = 0; r < SCAN_MAX_RANK; ++r) {
             T.nlt[lane][r] = 0u;
             T.rkey[lane][r] = (r < rk.num_rank && m < Nm) ? make_key(rk.dist[r * Nm + m], (unsigned)rk.idx[r * Nm + m]) : 0ull;
         }
@@ -142,23 +112,10 @@ __global__ __launch_bounds__(64) void sentences_scan_kernel(const float *__restr
     __syncthreads();
 
     const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    // bitonic sort of list p (slots >= cnt filled with KEY_MAX), cut back to the k smallest; returns the new fill
+    // list p sorted and cut back to the k smallest; returns the new fill
     auto compact = [&](int p, int cnt) -> int {
         unsigned long long *b = buf + (size_t)p * cap;
-        for (int i = cnt + lane; i < cap; i += 64) b[i] = SEN_KEY_MAX;
-        __syncthreads();
-        for (int size = 2; size <= cap; size <<= 1)
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int i = lane; i < cap; i += 64) {
-                    const int o = i ^ stride;
-                    if (o > i) {
-                        const bool asc = (i & size) == 0;
-                        const unsigned long long x = b[i], y = b[o];
-                        if ((x > y) == asc) { b[i] = y; b[o] = x; }
-                    }
-                }
-                __syncthreads();
-            }
+        wave_sort_keys(b, cnt, cap, lane);
         if (cnt >= k) {
             if (lane == 0) T.thr[p] = b[k - 1];
             cnt = k;
@@ -171,10 +128,10 @@ __global__ __launch_bounds__(64) void sentences_scan_kernel(const float *__restr
         const int64_t j = jb + lane;
         const bool live = j < j1;
         const float *sr = S + (live ? j : j1 - 1) * D;
-        float4 x[SEN_FAST_D / 4];
+        float4 x[SCAN_FAST_D / 4];
         if constexpr (FAST) {
 #pragma unroll
-            for (int k4 = 0; k4 < SEN_FAST_D / 4; ++k4) x[k4] = *reinterpret_cast<const float4 *>(sr + 4 * k4);
+            for (int k4 = 0; k4 < SCAN_FAST_D / 4; ++k4) x[k4] = *reinterpret_cast<const float4 *>(sr + 4 * k4);
         }
         const unsigned sid = (unsigned)(sent_base + j);
         int p = 0;
@@ -193,8 +150,8 @@ __global__ __launch_bounds__(64) void sentences_scan_kernel(const float *__restr
             const float *vb = V + (int64_t)(uni(T.c0[p]) + cmin) * D;
             int c = 0;
             if constexpr (FAST) {
-                for (; c + 4 <= nc; c += 4) sen_dist_fast<4>(x, vb + (int64_t)c * SEN_FAST_D, eps, ds + c * 64 + lane);
-                for (; c < nc; ++c) sen_dist_fast<1>(x, vb + (int64_t)c * SEN_FAST_D, eps, ds + c * 64 + lane);
+                for (; c + 4 <= nc; c += 4) sen_dist_fast<4>(x, vb + (int64_t)c * SCAN_FAST_D, eps, ds + c * 64 + lane);
+                for (; c < nc; ++c) sen_dist_fast<1>(x, vb + (int64_t)c * SCAN_FAST_D, eps, ds + c * 64 + lane);
             } else {
                 for (; c < nc; ++c) {
                     const float *vr = vb + (int64_t)c * D;
@@ -239,11 +196,11 @@ __global__ __launch_bounds__(64) void sentences_scan_kernel(const float *__restr
             int cnt = uni(T.cnt[r]);
             if (cnt > k) cnt = compact(r, cnt);
             unsigned long long *out = ws + ((size_t)ch * Nm + m) * k;
-            for (int i = lane; i < k; i += 64) out[i] = i < cnt ? buf[(size_t)r * cap + i] : SEN_KEY_EMPTY;
+            for (int i = lane; i < k; i += 64) out[i] = i < cnt ? buf[(size_t)r * cap + i] : SCAN_KEY_EMPTY;
         }
     }
-    if (lane < SEN_P * SEN_MAX_RANK) {
-        const int r = lane / SEN_MAX_RANK, rr = lane % SEN_MAX_RANK;
+    if (lane < SEN_P * SCAN_MAX_RANK) {
+        const int r = lane / SCAN_MAX_RANK, rr = lane % SCAN_MAX_RANK;
         const int64_t m = m0 + r;
         if (rr < rk.num_rank && m < Nm && T.nlt[r][rr])
             atomicAdd(reinterpret_cast<unsigned long long *>(rk.count_lt + (int64_t)rr * Nm + m), (unsigned long long)T.nlt[r][rr]);
@@ -257,8 +214,8 @@ extern "C" {
 
 size_t vfr_score_sentences_workspace_bytes(int64_t Nm, int64_t Ns, int k)
 {
-    if (Nm < 0 || Ns < 0 || k < 0 || k > vfr::SEN_MAX_K || Nm * (int64_t)(k > 0 ? k : 1) > 0x7FFFFFFF) return 0;
-    const vfr::SenPlan p = vfr::sen_plan(Nm, Ns);
+    if (Nm < 0 || Ns < 0 || k < 0 || k > vfr::SCAN_MAX_K || Nm * (int64_t)(k > 0 ? k : 1) > 0x7FFFFFFF) return 0;
+    const vfr::ScanPlan p = vfr::scan_plan(vfr::sen_tiles(Nm), Ns, vfr::SEN_TARGET_WAVES);
     return vfr::align_up((size_t)p.bound * (size_t)Nm * (size_t)k * 8 + 256, 256);
 }
 
@@ -267,34 +224,35 @@ int vfr_score_sentences_f32(const float *S, int64_t Ns, const float *V, const in
                             int k, float *out_dist, int64_t *out_idx, int num_rank, const float *rank_dist, const int64_t *rank_idx,
                             int64_t *count_lt, int *bad, void *workspace, size_t workspace_bytes, vfr_stream_t stream)
 {
-    VFR_REQUIRE(Ns >= 0 && Nm >= 0 && Nv >= 0 && total_clips >= 0 && D > 0 && k >= 0 && k <= vfr::SEN_MAX_K && max_clips >= 0 &&
+    VFR_REQUIRE(Ns >= 0 && Nm >= 0 && Nv >= 0 && total_clips >= 0 && D > 0 && k >= 0 && k <= vfr::SCAN_MAX_K && max_clips >= 0 &&
                 max_clips <= vfr::SEN_MAX_CLIPS && vid_base >= 0 && sent_base >= 0, VFR_EINVAL,
                 "vfr_score_sentences_f32: bad shape (k <= 448, max_clips <= 64, sizes, vid_base, sent_base >= 0)");
     VFR_REQUIRE(sent_base + Ns < (int64_t(1) << 32), VFR_EINVAL, "vfr_score_sentences_f32: sent_base + Ns must stay below 2^32");
     VFR_REQUIRE(Nm * (int64_t)(k > 0 ? k : 1) <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_sentences_f32: Nm * k must stay below 2^31");
-    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::SEN_MAX_RANK, VFR_EINVAL, "vfr_score_sentences_f32: num_rank %d (0 .. 4)", num_rank);
+    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::SCAN_MAX_RANK, VFR_EINVAL, "vfr_score_sentences_f32: num_rank %d (0 .. 4)", num_rank);
     VFR_REQUIRE(num_rank == 0 || (rank_dist && rank_idx && count_lt), VFR_EINVAL,
                 "vfr_score_sentences_f32: num_rank > 0 needs rank_dist, rank_idx and count_lt");
     VFR_REQUIRE(k == 0 || (out_dist && out_idx), VFR_EINVAL, "vfr_score_sentences_f32: k > 0 needs out_dist / out_idx");
     VFR_REQUIRE(Nm == 0 || probes, VFR_EINVAL, "vfr_score_sentences_f32: probes is null");
     VFR_REQUIRE(Ns == 0 || S, VFR_EINVAL, "vfr_score_sentences_f32: S is null");
     VFR_REQUIRE(Nv == 0 || (clip_offsets && (V || total_clips == 0)), VFR_EINVAL, "vfr_score_sentences_f32: null clip bank");
-    const vfr::SenPlan plan = vfr::sen_plan(Nm, Ns);
-    VFR_REQUIRE(plan.tiles * plan.chunks <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_sentences_f32: too many probe tiles");
+    const int64_t tiles = vfr::sen_tiles(Nm);
+    const vfr::ScanPlan plan = vfr::scan_plan(tiles, Ns, vfr::SEN_TARGET_WAVES);
+    VFR_REQUIRE(tiles * plan.chunks <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_sentences_f32: too many probe tiles");
     const size_t need = vfr_score_sentences_workspace_bytes(Nm, Ns, k);
     VFR_REQUIRE(workspace && workspace_bytes >= need, VFR_EWORKSPACE, "vfr_score_sentences_f32: workspace %zu < %zu bytes",
                 workspace_bytes, need);
     if (Nm == 0 || (k == 0 && num_rank == 0 && !bad)) return VFR_OK;
     hipStream_t st = vfr::as_stream(stream);
     const int rows = max_clips < 1 ? 1 : max_clips;
-    const int cap = vfr::sen_cap(k);
+    const int cap = vfr::scan_cap(k);
     const size_t lds = (size_t)rows * 64 * 4 + (size_t)vfr::SEN_P * cap * 8;             // <= 16 KB + 32 KB
     unsigned long long *keys = static_cast<unsigned long long *>(workspace);
     {
         vfr::ProfScope prof(vfr::SITE_SCORE_PAIRS, st);
-        vfr::SenRank rk{num_rank, rank_dist, rank_idx, count_lt};
-        const dim3 grid((unsigned)(plan.tiles * plan.chunks)), block(64);
-        const bool fast = D == vfr::SEN_FAST_D && (((uintptr_t)S) & 15) == 0 && (((uintptr_t)V) & 15) == 0;
+        vfr::ScanRank rk{num_rank, rank_dist, rank_idx, count_lt};
+        const dim3 grid((unsigned)(tiles * plan.chunks)), block(64);
+        const bool fast = vfr::rows_fast(S, V, D);
         if (fast)
             hipLaunchKernelGGL((vfr::sentences_scan_kernel<true>), grid, block, lds, st, S, Ns, V, clip_offsets, Nv, D, eps, probes, Nm,
                                vid_base, sent_base, k, cap, rk, rows, plan.chunks, plan.per, bad, keys);

@@ -6,8 +6,9 @@
 // (cand_off [Nq+1] int64, cand_vid [nnz] int32, corpus-global video indices, strictly ascending per query); entries outside
 // [vid_base, vid_base + Nv) belong to another shard and are skipped, so every shard takes the same lists.
 //
-// Kernels (a translation unit of its own: the arithmetic is the canonical chain of vtk_exact_kernel, restated here, so the code
-// objects of score.o do not change):
+// Kernels (a translation unit of its own: the arithmetic is the canonical chain of vtk_exact_kernel, written out here, so the code
+// objects of score.o do not change; the key constants, the rank-key counters and the sort of the key buffer are those of
+// scan_common.h):
 //   subset_plan_kernel   one workgroup: chunk_off[q] = sum over q' < q of ceil(len_q' / 64) (a list is cut into chunks of 64
 //                        entries), clamped to the host's bound on the chunk count; flags lists longer than max_list
 //   subset_scan_kernel   one wave per chunk (a flattened grid: a query with 10 000 candidates and 4 999 with 10 cost 157 + 4 999
@@ -22,21 +23,15 @@
 //                        padded with (+inf, -1)
 // Workspace: chunk_off [Nq+1] and the keys: (nnz + 63 Nq) / 64 chunks x k for moments (no more than Nq ceil(max_list / 64)),
 // nnz for videos.  Nothing is of size Nq x Nv and nothing waits for the host.
-#include "vfr_common.h"
-#include "vfr_math.h"
+#include "scan_common.h"
 
 namespace vfr {
 namespace {
 
 constexpr int SUB_LANES = 64;                       // list entries per chunk (= wave lanes)
 constexpr int SUB_MAX_CLIPS = 64;                   // as the fused scorer (NMAX_FUSED)
-constexpr int SUB_MAX_K = 448;
-constexpr int SUB_MAX_RANK = 4;
 constexpr int SUB_BUF = 1024;                       // per-wave key buffer of the moment level (>= k + 64)
 constexpr int SUB_SORT = 512;                       // pool of the top-k kernel (>= k)
-constexpr int SUB_FAST_D = 100;
-constexpr unsigned long long SUB_KEY_MAX = ~0ull;                 // padding of the workspace
-constexpr unsigned long long SUB_KEY_EMPTY = 0x7F800000FFFFFFFFull;   // (+inf, max id): no moment
 
 // the host's bound on the total number of chunks: sum ceil(len / 64) <= (nnz + 63 Nq) / 64, and <= Nq ceil(max_list / 64)
 int64_t sub_chunk_bound(int64_t Nq, int64_t nnz, int64_t max_list)
@@ -94,19 +89,12 @@ __global__ __launch_bounds__(1024) void subset_plan_kernel(const int64_t *__rest
 }
 
 // ---- one wave per (query, chunk of 64 list entries) ----
-struct SubRank {
-    int num_rank;
-    const float *dist;        // [num_rank, Nq]
-    const int64_t *idx;
-    int64_t *count_lt;
-};
-
 __global__ __launch_bounds__(64) void subset_scan_kernel(const float *__restrict__ Q, int64_t Nq, const float *__restrict__ V,
                                                          const int32_t *__restrict__ clip_off, const int64_t *__restrict__ mom_off,
                                                          int Nv, int D, float eps, int64_t id_base, int64_t vid_base,
                                                          const int64_t *__restrict__ cand_off, const int32_t *__restrict__ cand_vid,
                                                          int64_t nnz, int64_t max_list, const int *__restrict__ chunk_off,
-                                                         int level, int k, SubRank rk, int ds_rows, int *__restrict__ bad,
+                                                         int level, int k, ScanRank rk, int ds_rows, int *__restrict__ bad,
                                                          unsigned long long *__restrict__ ws)
 {
     extern __shared__ __attribute__((aligned(16))) float ssm[];
@@ -150,12 +138,12 @@ __global__ __launch_bounds__(64) void subset_scan_kernel(const float *__restrict
         for (int c = 0; c < n; ++c) {
             const float *vr = V + (int64_t)(c0 + c) * D;
             float acc = 0.0f;
-            if (D == SUB_FAST_D && vec4) {                // the whole row requested at once, then the k-ascending chain
-                float4 x[SUB_FAST_D / 4];
+            if (D == SCAN_FAST_D && vec4) {                // the whole row requested at once, then the k-ascending chain
+                float4 x[SCAN_FAST_D / 4];
 #pragma unroll
-                for (int k4 = 0; k4 < SUB_FAST_D / 4; ++k4) x[k4] = *reinterpret_cast<const float4 *>(vr + 4 * k4);
+                for (int k4 = 0; k4 < SCAN_FAST_D / 4; ++k4) x[k4] = *reinterpret_cast<const float4 *>(vr + 4 * k4);
 #pragma unroll
-                for (int k4 = 0; k4 < SUB_FAST_D / 4; ++k4) {
+                for (int k4 = 0; k4 < SCAN_FAST_D / 4; ++k4) {
                     const float4 y = *reinterpret_cast<const float4 *>(qs + 4 * k4);
                     float t = (x[k4].x - y.x) + eps; acc = __builtin_fmaf(t, t, acc);
                     t = (x[k4].y - y.y) + eps; acc = __builtin_fmaf(t, t, acc);
@@ -179,14 +167,14 @@ __global__ __launch_bounds__(64) void subset_scan_kernel(const float *__restrict
             ds[c * 64 + lane] = __builtin_sqrtf(acc);
         }
     }
-    unsigned long long rkey[SUB_MAX_RANK];
+    unsigned long long rkey[SCAN_MAX_RANK];
 #pragma unroll
-    for (int r = 0; r < SUB_MAX_RANK; ++r)
+    for (int r = 0; r < SCAN_MAX_RANK; ++r)
         rkey[r] = r < rk.num_rank ? make_key(rk.dist[r * Nq + q], (unsigned)rk.idx[r * Nq + q]) : 0ull;
-    int nlt[SUB_MAX_RANK] = {0, 0, 0, 0};
+    int nlt[SCAN_MAX_RANK] = {0, 0, 0, 0};
 
     if (level == VFR_SUBSET_VIDEOS) {
-        unsigned long long best = SUB_KEY_EMPTY;
+        unsigned long long best = SCAN_KEY_EMPTY;
         for (int s = 0; s < n; ++s) {
             float sum = 0.0f;
             for (int e2 = s; e2 < n; ++e2) {
@@ -197,35 +185,19 @@ __global__ __launch_bounds__(64) void subset_scan_kernel(const float *__restrict
                 best = key < best ? key : best;
             }
         }
-        if (n > 0) {
-#pragma unroll
-            for (int r = 0; r < SUB_MAX_RANK; ++r) nlt[r] += (r < rk.num_rank && best < rkey[r]) ? 1 : 0;
-        }
-        if (listed) ws[e] = v >= 0 ? best : SUB_KEY_MAX;
+        if (n > 0) scan_rank_count(rk.num_rank, rkey, best, nlt);
+        if (listed) ws[e] = v >= 0 ? best : SCAN_KEY_MAX;
     } else {
         // the wave-uniform loop over the widest triangle of the chunk: a lane past its own video's end takes no part
         int nmax = n;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) { const int x = __shfl_xor(nmax, o, 64); nmax = x > nmax ? x : nmax; }
-        unsigned long long thr = SUB_KEY_MAX;             // keys >= thr cannot be among the chunk's k smallest
+        unsigned long long thr = SCAN_KEY_MAX;             // keys >= thr cannot be among the chunk's k smallest
         int cnt = 0;                                      // keys in buf (wave-uniform)
         const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
         auto compact = [&]() {
-            // bitonic sort of buf[0..SUB_BUF) (slots >= cnt hold SUB_KEY_MAX), keep the k smallest
-            for (int i = cnt + lane; i < SUB_BUF; i += 64) buf[i] = SUB_KEY_MAX;
-            __syncthreads();
-            for (int size = 2; size <= SUB_BUF; size <<= 1)
-                for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                    for (int i = lane; i < SUB_BUF; i += 64) {
-                        const int p = i ^ stride;
-                        if (p > i) {
-                            const bool asc = (i & size) == 0;
-                            const unsigned long long x = buf[i], y = buf[p];
-                            if ((x > y) == asc) { buf[i] = y; buf[p] = x; }
-                        }
-                    }
-                    __syncthreads();
-                }
+            // buf[0..SUB_BUF) sorted, keep the k smallest
+            wave_sort_keys(buf, cnt, SUB_BUF, lane);
             if (cnt >= k) { thr = buf[k - 1]; cnt = k; }
         };
         for (int s = 0; s < nmax; ++s) {
@@ -236,10 +208,7 @@ __global__ __launch_bounds__(64) void subset_scan_kernel(const float *__restrict
                 sum = e2 == s ? de : sum + de;
                 const float sc = sum / (float)(e2 - s + 1);
                 const unsigned long long key = make_key(sc, (unsigned)(mbase + moment_index(n, s, e2)));
-                if (live) {
-#pragma unroll
-                    for (int r = 0; r < SUB_MAX_RANK; ++r) nlt[r] += (r < rk.num_rank && key < rkey[r]) ? 1 : 0;
-                }
+                if (live) scan_rank_count(rk.num_rank, rkey, key, nlt);
                 if (k > 0) {
                     const bool take = live && key < thr;
                     const unsigned long long m = __ballot(take);
@@ -253,12 +222,12 @@ __global__ __launch_bounds__(64) void subset_scan_kernel(const float *__restrict
             __syncthreads();
             compact();
             unsigned long long *out = ws + (size_t)chunk * k;
-            for (int i = lane; i < k; i += 64) out[i] = i < cnt ? buf[i] : SUB_KEY_MAX;
+            for (int i = lane; i < k; i += 64) out[i] = i < cnt ? buf[i] : SCAN_KEY_MAX;
         }
     }
     if (rk.num_rank > 0) {
 #pragma unroll
-        for (int r = 0; r < SUB_MAX_RANK; ++r) {
+        for (int r = 0; r < SCAN_MAX_RANK; ++r) {
             int x = nlt[r];
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
@@ -325,7 +294,7 @@ __global__ __launch_bounds__(256) void subset_topk_kernel(const unsigned long lo
         len = (chunk_off[q + 1] - chunk_off[q]) * k;
     }
     // threshold = the k-th smallest entry (KEY_MAX padding included; real keys of a valid list are distinct: ids are)
-    unsigned long long thr = SUB_KEY_MAX;
+    unsigned long long thr = SCAN_KEY_MAX;
     if (len > k) {
         const unsigned hi = sub_radix_kth32([&](int i) { return (unsigned)(row[i] >> 32); }, len, k, hist, sw);
         int below = 0;
@@ -340,11 +309,11 @@ __global__ __launch_bounds__(256) void subset_topk_kernel(const unsigned long lo
         thr = ((unsigned long long)hi << 32) | lo;
     }
     if (threadIdx.x == 0) npool = 0;
-    for (int i = threadIdx.x; i < SUB_SORT; i += 256) pool[i] = SUB_KEY_MAX;
+    for (int i = threadIdx.x; i < SUB_SORT; i += 256) pool[i] = SCAN_KEY_MAX;
     __syncthreads();
     for (int i = threadIdx.x; i < len; i += 256) {
         const unsigned long long x = row[i];
-        if (x < SUB_KEY_EMPTY && x <= thr) { const int s = atomicAdd(&npool, 1); if (s < SUB_SORT) pool[s] = x; }
+        if (x < SCAN_KEY_EMPTY && x <= thr) { const int s = atomicAdd(&npool, 1); if (s < SUB_SORT) pool[s] = x; }
     }
     __syncthreads();
     for (int size = 2; size <= SUB_SORT; size <<= 1) {
@@ -389,7 +358,7 @@ extern "C" {
 
 size_t vfr_score_subset_workspace_bytes(int64_t Nq, int64_t nnz, int64_t max_list, int k, int level)
 {
-    if (Nq < 0 || nnz < 0 || max_list < 0 || k < 0 || k > vfr::SUB_MAX_K || (level != VFR_SUBSET_MOMENTS && level != VFR_SUBSET_VIDEOS))
+    if (Nq < 0 || nnz < 0 || max_list < 0 || k < 0 || k > vfr::SCAN_MAX_K || (level != VFR_SUBSET_MOMENTS && level != VFR_SUBSET_VIDEOS))
         return 0;
     return vfr::carve_subset(nullptr, Nq, nnz, max_list, k, level).total;
 }
@@ -404,14 +373,14 @@ int vfr_score_subset_f32(const float *Q, int64_t Nq, const float *V, const int32
     (void)min_clips;
     VFR_REQUIRE(level == VFR_SUBSET_MOMENTS || level == VFR_SUBSET_VIDEOS, VFR_EINVAL,
                 "vfr_score_subset_f32: level %d (0 = moments, 1 = videos)", level);
-    VFR_REQUIRE(Nq >= 0 && Nv >= 0 && total_clips >= 0 && D > 0 && k >= 0 && k <= vfr::SUB_MAX_K && max_clips >= 0 &&
+    VFR_REQUIRE(Nq >= 0 && Nv >= 0 && total_clips >= 0 && D > 0 && k >= 0 && k <= vfr::SCAN_MAX_K && max_clips >= 0 &&
                 max_clips <= vfr::SUB_MAX_CLIPS && id_base >= 0 && vid_base >= 0 && nnz >= 0 && max_list >= 0, VFR_EINVAL,
                 "vfr_score_subset_f32: bad shape (k <= 448, max_clips <= 64, id_base, vid_base, nnz, max_list >= 0)");
     VFR_REQUIRE(id_base + (int64_t)total_clips * (max_clips + 1) / 2 <= (int64_t(1) << 32), VFR_EINVAL,
                 "vfr_score_subset_f32: id_base + moments must stay below 2^32");
     VFR_REQUIRE(Nq * (int64_t)k <= 0x7FFFFFFF && nnz <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_subset_f32: Nq * k and nnz must stay below 2^31");
     VFR_REQUIRE(vfr::sub_chunk_bound(Nq, nnz, max_list) <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_subset_f32: too many list chunks");
-    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::SUB_MAX_RANK, VFR_EINVAL, "vfr_score_subset_f32: num_rank %d (0 .. 4)", num_rank);
+    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::SCAN_MAX_RANK, VFR_EINVAL, "vfr_score_subset_f32: num_rank %d (0 .. 4)", num_rank);
     VFR_REQUIRE(num_rank == 0 || (rank_dist && rank_idx && count_lt), VFR_EINVAL,
                 "vfr_score_subset_f32: num_rank > 0 needs rank_dist, rank_idx and count_lt");
     VFR_REQUIRE(k == 0 || (out_dist && out_idx), VFR_EINVAL, "vfr_score_subset_f32: k > 0 needs out_dist / out_idx");
@@ -436,7 +405,7 @@ int vfr_score_subset_f32(const float *Q, int64_t Nq, const float *V, const int32
     }
     if (bound > 0 && Nv > 0) {
         vfr::ProfScope prof(vfr::SITE_SCORE_PAIRS, st);
-        vfr::SubRank rk{num_rank, rank_dist, rank_idx, count_lt};
+        vfr::ScanRank rk{num_rank, rank_dist, rank_idx, count_lt};
         hipLaunchKernelGGL(vfr::subset_scan_kernel, dim3((unsigned)bound), dim3(64), lds, st, Q, Nq, V, clip_offsets, moment_offsets, Nv, D,
                            eps, id_base, vid_base, cand_off, cand_vid, nnz, max_list, w.chunk_off, level, k, rk, rows, bad, w.keys);
         VFR_CHECK_LAUNCH("subset_scan_kernel");
