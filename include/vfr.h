@@ -499,6 +499,23 @@ int vfr_score_prior_f32(const float *Q, int64_t Nq, const float *V, const int32_
  * reversed != 0 runs the reference chain k-descending (what a failing check looks like).  The Python layer runs it once per
  * process before the first "mfma" / "bf16" scoring call and falls back to the exact kernels if it fails.          */
 int vfr_mfma_selfcheck(const float *A, const float *B, int K, int reversed, int *mismatches, vfr_stream_t stream);
+/* int8 arm of the self-check: what the int8 operand mode of the pre-filter ("score_i8") assumes about v_mfma_i32_16x16x64_i8 --
+ * its lane map and exact, accumulated products.  A, B: device [16, 128] int8 (16-byte aligned; make them asymmetric): C = A B^T
+ * over two chained k-steps on the matrix pipe against integer dot products on the vector ALU; *mismatches (device int) = elements
+ * that differ.  permuted != 0 compares with the TRANSPOSED product (what a wrong lane map looks like).  The Python layer runs it
+ * with the fp32 arm; a device that fails only this arm scores with the fp32 operands ("score_i8" 0) and a warning.          */
+int vfr_mfma_selfcheck_i8(const int8_t *A, const int8_t *B, int permuted, int *mismatches, vfr_stream_t stream);
+/* TEST HOOK of the int8 operand mode (not on any hot path): runs the mode's pre-passes on (Q, V) in `workspace`
+ * (>= vfr_score_topk_mfma_workspace_bytes(Nq, Nv, total_clips, 0)) and copies out, all device pointers: the limb planes
+ * vlimbs [total_clips, 3, 128] / qlimbs [Nq, 3, 128] (digit i of X = sum digit_i 256^i; bytes 100 .. 127 zero), bank_const [4] =
+ * {s_v, max |v - X / s_v|, max |X_v|_1 / s_v, max |v_k - mu_k|}, query_const [Nq, 2] = {|q - mu|_1, max |q - X / s_q|},
+ * query_scale [groups] = s_q and query_factor [groups] = fl(-512 / (s_q s_v)) per 64-query group, qmeta [Nq, 4] = {b_q, 0, E2,
+ * R + |q|}, va [total_clips] = a_c, mu [128], and ring [Nq, total_clips] = the approximate d^2 - b_q of every (query, clip) as
+ * the scoring kernel's device functions compute them (16-clip tiles from clip 0).  D = 100.                                 */
+int vfr_score_i8_debug(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, int Nv, int total_clips, int D,
+                       float eps, void *workspace, size_t workspace_bytes, int8_t *vlimbs, int8_t *qlimbs, double *bank_const,
+                       double *query_const, double *query_scale, float *query_factor, float *qmeta, float *va, float *mu,
+                       float *ring, vfr_stream_t stream);
 /* merge G per-shard top-k lists (after the RCCL all-gather): part_dist/part_idx
  * [G, Nq, k] -> out [Nq, k], same (distance, id) order.                                        */
 int vfr_topk_merge_f32(const float *part_dist, const int64_t *part_idx, int G, int64_t Nq, int k, float *out_dist,
@@ -688,7 +705,10 @@ int vfr_math_f32(int op, const float *x, const float *y, float *out, int64_t n, 
  * a wave are left undecided by the video's smallest / largest clip distance -- those are re-counted exactly; default 8, -1: off),
  * "score_sort" 1|0|2 (the pre-filter pass with rank keys runs on the batch sorted by difficulty from 1024 queries x 4096 videos
  * on | caller's order | sorted whatever the size), "score_hist" 1|0 (the main top-k launch tightens its threshold from a histogram
- * of the candidates found so far | stage B's threshold throughout) -- same bits either way.  Options are process-global (see Conventions).        */
+ * of the candidates found so far | stage B's threshold throughout), "score_i8" 1|0 (vfr_score_topk_mfma, f32: the pre-filter's
+ * approximate GEMM runs on int8 limbs of the centred rows -- exact integer products on v_mfma_i32_16x16x64_i8, the margin built
+ * from the computed quantisation error | on the fp32 rows, v_mfma_f32_16x16x4_f32; the bank-side products of one form are
+ * recomputed when the other is asked for) -- same bits either way.  Options are process-global (see Conventions).        */
 int vfr_set_option(const char *name, int value);
 int vfr_get_option(const char *name);
 /* vfr_set_option("profile", 1): every instrumented launch is bracketed by two hipEvents recorded on

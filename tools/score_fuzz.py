@@ -22,6 +22,7 @@ for it in range(ncfg):
         _vfr.set_option("score_sort", int(rs.choice([1, 2, 2])))
         _vfr.set_option("score_defer", int(rs.choice([-1, 0, 8, 8, 20])))
         _vfr.set_option("score_hist", int(rs.choice([0, 1, 1])))
+        _vfr.set_option("score_i8", int(rs.choice([0, 1, 1])))          # int8 limbs or fp32 rows as the pre-filter's operands
     shape = rs.choice(["n21", "n6", "ragged56", "ragged21"])
     nv = int(rs.choice([1, 3, 31, 33, 100, 257, 600, 1100, 3000]))
     nq = int(rs.choice([1, 5, 63, 64, 65, 200, 1000]))

@@ -87,6 +87,8 @@ SIGNATURES = {
     "vfr_score_prior_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _i32, _vp, _vp, _i32,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "vfr_mfma_selfcheck_i8": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "vfr_score_i8_debug": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _f32, _vp, ctypes.c_size_t] + [_vp] * 11),
     "vfr_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "vfr_topk_pack_keys": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "vfr_topk_merge_keys": (_i32, [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
@@ -456,9 +458,28 @@ def mfma_selfcheck(device=None, reversed_reference: bool = False) -> int:
     return int(mis.item())
 
 
+def mfma_selfcheck_i8(device=None, permuted_reference: bool = False) -> int:
+    """The int8 arm (include/vfr.h vfr_mfma_selfcheck_i8): elements (of 256) on which the matrix pipe's 16x16x128 int8 product
+    differs from integer dot products on the vector ALU, on asymmetric data that reaches -128 and 127.  0 on a conforming
+    device; ``permuted_reference`` compares with the transposed product (what a failing check looks like).  SYNCHRONISES."""
+    device = torch.device(device if device is not None else "cuda")
+    rs = np.random.RandomState(2025)
+    A = rs.randint(-128, 128, (16, 128)).astype(np.int8)
+    B = rs.randint(-128, 128, (16, 128)).astype(np.int8)
+    A[:, 0], A[:, 1], B[:, 0], B[:, 1] = -128, 127, 127, -128
+    B[:, 64:] //= 2                                                         # the two k-steps, and the two operands, are not alike
+    a, b = torch.from_numpy(A).to(device), torch.from_numpy(B).to(device)
+    mis = torch.zeros(1, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(lib().vfr_mfma_selfcheck_i8(a.data_ptr(), b.data_ptr(), 1 if permuted_reference else 0, mis.data_ptr(), _stream()),
+               "vfr_mfma_selfcheck_i8")
+    return int(mis.item())
+
+
 def _mfma_mode_ok(device) -> bool:
     """The first "mfma" / "bf16" scoring call on a device runs the self-check; a device that fails it gets the exact kernels
-    (and a warning) for the rest of the process: the pre-filter's margins assume the checked arithmetic."""
+    (and a warning) for the rest of the process: the pre-filter's margins assume the checked arithmetic.  A device that fails
+    only the int8 arm keeps the pre-filter on its fp32 operands ("score_i8" 0: process-global, like every option)."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     ok = _MFMA_CHECKED.get(idx)
     if ok is None:
@@ -467,7 +488,31 @@ def _mfma_mode_ok(device) -> bool:
             import warnings
             warnings.warn("vfr: the MFMA self-check failed on this device (v_mfma_f32_16x16x4_f32 is not a k-ascending fp32 fma "
                           "chain here); scoring falls back to the exact kernels")
+        elif mfma_selfcheck_i8(device) != 0:
+            import warnings
+            set_option("score_i8", 0)
+            warnings.warn("vfr: the int8 arm of the MFMA self-check failed on this device (v_mfma_i32_16x16x64_i8 does not have the "
+                          "assumed lane map); the pre-filter runs on its fp32 operands")
     return ok
+
+
+def score_i8_debug(Q: torch.Tensor, bank: "VideoBank", eps: float = 1e-6) -> dict:
+    """TEST HOOK (include/vfr.h vfr_score_i8_debug): the products of the int8 operand mode's pre-passes and the ring values
+    d~^2 - b_q of every (query, clip), as numpy arrays.  SYNCHRONISES."""
+    Q = _dev(Q, torch.float32, "Q")
+    Nq, C, dev = Q.shape[0], bank.total_clips, Q.device
+    groups = (Nq + 63) // 64
+    nbytes = lib().vfr_score_topk_mfma_workspace_bytes(Nq, bank.num_videos, C, 0)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = {"vlimbs": torch.zeros(C, 3, 128, dtype=torch.int8, device=dev), "qlimbs": torch.zeros(Nq, 3, 128, dtype=torch.int8, device=dev),
+           "bank_const": torch.zeros(4, dtype=torch.float64, device=dev), "query_const": torch.zeros(Nq, 2, dtype=torch.float64, device=dev),
+           "query_scale": torch.zeros(groups, dtype=torch.float64, device=dev), "query_factor": torch.zeros(groups, dtype=torch.float32, device=dev),
+           "qmeta": torch.zeros(Nq, 4, dtype=torch.float32, device=dev), "va": torch.zeros(C, dtype=torch.float32, device=dev),
+           "mu": torch.zeros(128, dtype=torch.float32, device=dev), "ring": torch.zeros(Nq, C, dtype=torch.float32, device=dev)}
+    _check(lib().vfr_score_i8_debug(Q.data_ptr(), Nq, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.num_videos, C, bank.dim, eps,
+                                    ws.data_ptr(), nbytes, *[t.data_ptr() for t in out.values()], _stream()), "vfr_score_i8_debug")
+    torch.cuda.synchronize(dev)
+    return {k: t.cpu().numpy() for k, t in out.items()}
 
 
 def _bank_args(Q: torch.Tensor, bank: VideoBank, eps: float):

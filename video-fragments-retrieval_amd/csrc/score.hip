@@ -214,6 +214,7 @@ struct ScoreArgs {
     const int *group_mask;                            // != null: only query groups g with group_mask[g] != 0 are answered (MFMA fallback)
     const struct MfmaArgs *mf_host;                   // HOST pointer, != null: launch the MFMA pre-filter kernel (score_mfma.h)
     int mf_bf16;
+    int mf_i8;                                        // the pre-filter's operands are int8 limbs (score_mfma.h)
 #ifdef VFR_SCORE_STAMPS
     unsigned long long *stamps;                       // debug build: per-phase s_memtime totals of the fused kernel
 #endif
@@ -1281,8 +1282,8 @@ static int launch_mfma(const ScoreArgs &a, hipStream_t st, int *cap_transposed)
             else                 { if (kpl == 4 && NTV == 6) VFR_MF(NTV, (NTV == 6 ? 4 : 8), 2, true, BF); else VFR_MF(NTV, 8, 2, true, BF); } \
         } else VFR_MF(NTV, 4, 2, false, BF);                                                                              \
     } while (0)
-    if (NT == 6) { if (a.mf_bf16) VFR_MF_NT(6, true); else VFR_MF_NT(6, false); }
-    else         { if (a.mf_bf16) VFR_MF_NT(21, true); else VFR_MF_NT(21, false); }
+    if (NT == 6) { if (a.mf_bf16) VFR_MF_NT(6, 1); else if (a.mf_i8) VFR_MF_NT(6, 2); else VFR_MF_NT(6, 0); }
+    else         { if (a.mf_bf16) VFR_MF_NT(21, 1); else if (a.mf_i8) VFR_MF_NT(21, 2); else VFR_MF_NT(21, 0); }
 #undef VFR_MF_NT
 #undef VFR_MF
     VFR_CHECK_LAUNCH("score_mfma_kernel");
@@ -1535,6 +1536,7 @@ struct MfmaWs {
     float *rv; BankSig *sig; unsigned long long *hash_now; int *stale; int *fallback; unsigned long long *pairs_total; unsigned long long *cnt_ws; size_t zero_bytes; char *zero_base;
     float *va; float4 *qmeta; unsigned *tab; unsigned *wmax, *qbound; unsigned short *vb; ulonglong2 *amb; int tasks, groups;
     float *mu, *vc, *qc; double *mean_partial; int mean_blocks, mean_rows;
+    signed char *vl, *ql; float2 *mean_minmax; double *bankc; float *qf; double2 *qdbg; double *qscale;   // int8 operand mode
     void *topk; size_t topk_bytes; size_t total;
     int *perm, *diff; unsigned *hist; uint2 *hrange; float *Qs, *rds; int64_t *ris, *seeds, *cnts; float *ods; int64_t *ois;
 };
@@ -1554,7 +1556,12 @@ static MfmaWs carve_mfma(void *base, int64_t Nq, int Nv, int total_clips, int k)
     w.mean_blocks = (int)cdiv(total_clips > 0 ? total_clips : 1, w.mean_rows);
     w.mu = reinterpret_cast<float *>(take(128 * 4));
     w.mean_partial = reinterpret_cast<double *>(take((size_t)w.mean_blocks * 128 * 8));
+    w.mean_minmax = reinterpret_cast<float2 *>(take((size_t)w.mean_blocks * 128 * 8));
+    w.bankc = reinterpret_cast<double *>(take(I8C_COUNT * 8));
+    // the centred rows: fp32 copy (400 B per clip) or int8 limb planes (384 B) -- never both (BankSig::has_i8)
+    static_assert(I8_ROW <= FAST_D * 4, "the limb planes fit the region of the fp32 copy");
     w.vc = reinterpret_cast<float *>(take((size_t)total_clips * FAST_D * 4));
+    w.vl = reinterpret_cast<signed char *>(w.vc);
     w.va = reinterpret_cast<float *>(take((size_t)total_clips * 4));
     w.vb = reinterpret_cast<unsigned short *>(take((size_t)total_clips * 128 * 2));
     // zeroed at every call
@@ -1572,6 +1579,10 @@ static MfmaWs carve_mfma(void *base, int64_t Nq, int Nv, int total_clips, int k)
     w.hrange = reinterpret_cast<uint2 *>(take(k > 0 ? (size_t)Nq * 8 : 0));
     w.zero_bytes = off - z0;
     w.qc = reinterpret_cast<float *>(take((size_t)Nq * FAST_D * 4));
+    w.ql = reinterpret_cast<signed char *>(w.qc);                        // (the same rule for the query rows of a call)
+    w.qf = reinterpret_cast<float *>(take((size_t)g * 4));
+    w.qscale = reinterpret_cast<double *>(take((size_t)g * 8));
+    w.qdbg = reinterpret_cast<double2 *>(take((size_t)Nq * 16));
     w.qmeta = reinterpret_cast<float4 *>(take((size_t)Nq * 16));
     w.tab = reinterpret_cast<unsigned *>(take((size_t)Nq * 2 * 21 * MF_TAB * 4));
     // ambiguous-pair bitmap: two 64-bit masks per (video, query group), every slot written by exactly one wave per call
@@ -2140,6 +2151,7 @@ int vfr_score_topk_mfma(const float *Q, int64_t Nq, const float *V, const int32_
     VFR_REQUIRE(id_base >= 0, VFR_EINVAL, "vfr_score_topk_mfma: bad id_base");
     hipStream_t st = vfr::as_stream(stream);
     const bool bf16 = dtype == VFR_MFMA_BF16;
+    const bool i8 = !bf16 && vfr::opt_score_i8() != 0;
     const int NT = max_clips <= 6 ? 6 : 21;
     const int kp = k > 0 ? k + vfr::MF_EXTRA : 0;
     vfr::MfmaWs mw = vfr::carve_mfma(workspace, Nq, Nv, total_clips, k);
@@ -2193,6 +2205,7 @@ int vfr_score_topk_mfma(const float *Q, int64_t Nq, const float *V, const int32_
     vfr::MfmaArgs m{};
     m.va = mw.va; m.qmeta = mw.qmeta; m.tab = mw.tab; m.cnt_ws = mw.cnt_ws; m.amb = mw.amb; m.pairs_total = mw.pairs_total; m.wmax = mw.wmax;
     m.fallback = mw.fallback; m.vb = bf16 ? mw.vb : nullptr; m.rv = mw.rv; m.vc = mw.vc; m.qc = mw.qc;
+    m.vl = mw.vl; m.ql = mw.ql; m.qf = mw.qf;
     m.qbound = mw.qbound; m.defer_max = vfr::opt_score_defer();
     m.diff = diff_plan ? mw.diff : nullptr; m.perm = sorted ? mw.perm : nullptr;
     m.hist = (k > 0 && vfr::opt_score_hist()) ? mw.hist : nullptr; m.hrange = mw.hrange;
@@ -2203,20 +2216,31 @@ int vfr_score_topk_mfma(const float *Q, int64_t Nq, const float *V, const int32_
             // caller claims BANK_READY AND the bank still hashes to the signature stored with the products (score_mfma.h)
             vfr::BankSig now{};
             now.total_clips = total_clips; now.Nv = Nv; now.D = D; now.eps_bits = __builtin_bit_cast(unsigned, eps); now.has_bf16 = bf16 ? 1 : 0;
+            now.has_i8 = i8 ? 1 : 0;
             const int64_t nwords = (int64_t)total_clips * D;
             int hb = (int)vfr::cdiv(nwords, 256 * 4 * 8);
             hb = hb < 1 ? 1 : (hb > 2048 ? 2048 : hb);
             hipLaunchKernelGGL(vfr::mfma_bank_hash_kernel, dim3((unsigned)hb), dim3(256), 0, st, reinterpret_cast<const unsigned *>(V), nwords,
                                reinterpret_cast<const unsigned *>(clip_offsets), (int64_t)Nv + 1, mw.hash_now);
-            hipLaunchKernelGGL(vfr::mfma_bank_check_kernel, dim3(1), dim3(1), 0, st, mw.hash_now, now, bank_ready ? 1 : 0, mw.sig, mw.stale, mw.rv);
+            hipLaunchKernelGGL(vfr::mfma_bank_check_kernel, dim3(1), dim3(1), 0, st, mw.hash_now, now, bank_ready ? 1 : 0, mw.sig, mw.stale, mw.rv,
+                               mw.bankc);
             hipLaunchKernelGGL(vfr::mfma_mean_partial_kernel, dim3((unsigned)mw.mean_blocks), dim3(1024), 0, st, V, total_clips, D, mw.mean_rows,
-                               mw.mean_partial, mw.stale);
-            hipLaunchKernelGGL(vfr::mfma_mean_final_kernel, dim3(1), dim3(1024), 0, st, mw.mean_partial, mw.mean_blocks, D, total_clips, mw.mu, mw.stale);
-            hipLaunchKernelGGL(vfr::mfma_prep_v_kernel, dim3((unsigned)vfr::cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps,
-                               mw.mu, mw.vc, mw.va, mw.rv, bf16 ? mw.vb : nullptr, mw.stale);
+                               mw.mean_partial, mw.stale, i8 ? mw.mean_minmax : nullptr);
+            hipLaunchKernelGGL(vfr::mfma_mean_final_kernel, dim3(1), dim3(1024), 0, st, mw.mean_partial, mw.mean_blocks, D, total_clips, mw.mu, mw.stale,
+                               i8 ? mw.mean_minmax : nullptr, i8 ? mw.bankc : nullptr);
+            if (i8)
+                hipLaunchKernelGGL(vfr::mfma_prep_v_i8_kernel, dim3((unsigned)vfr::cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps,
+                                   mw.mu, mw.vl, mw.va, mw.rv, mw.bankc, mw.stale);
+            else
+                hipLaunchKernelGGL(vfr::mfma_prep_v_kernel, dim3((unsigned)vfr::cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps,
+                                   mw.mu, mw.vc, mw.va, mw.rv, bf16 ? mw.vb : nullptr, mw.stale);
         }
-        hipLaunchKernelGGL(vfr::mfma_prep_q_kernel, dim3((unsigned)vfr::cdiv(Nq, 16)), dim3(256), 0, st, Q, Nq, D, eps, mw.mu, mw.qc, mw.rv,
-                           num_rank, rank_dist, mw.qmeta);
+        if (i8)
+            hipLaunchKernelGGL(vfr::mfma_prep_q_i8_kernel, dim3((unsigned)vfr::cdiv(Nq, 64)), dim3(1024), 0, st, Q, Nq, D, eps, mw.mu, mw.ql, mw.rv,
+                               mw.bankc, num_rank, rank_dist, mw.qmeta, mw.qf, mw.qdbg, mw.qscale);
+        else
+            hipLaunchKernelGGL(vfr::mfma_prep_q_kernel, dim3((unsigned)vfr::cdiv(Nq, 16)), dim3(256), 0, st, Q, Nq, D, eps, mw.mu, mw.qc, mw.rv,
+                               num_rank, rank_dist, mw.qmeta);
         if (num_rank > 0) {
             const dim3 tg((unsigned)vfr::cdiv(Nq * num_rank * NT, 256));
             if (NT == 6)
@@ -2237,7 +2261,7 @@ int vfr_score_topk_mfma(const float *Q, int64_t Nq, const float *V, const int32_
     a.ds_rows = max_clips < 1 ? 1 : max_clips;
     a.total_clips = total_clips;
     a.min_clips = min_clips;
-    a.mf_host = &m; a.mf_bf16 = bf16 ? 1 : 0;
+    a.mf_host = &m; a.mf_bf16 = bf16 ? 1 : 0; a.mf_i8 = i8 ? 1 : 0;
     if (int rc = vfr::run_pass(a, w, thr_seed != nullptr, nullptr, nullptr, kp > 0 ? w.pre_keys : nullptr, st)) return rc;
     int g, c;
     vfr::plan_tasks(Nq, Nv, &g, &c);
@@ -2460,6 +2484,62 @@ __global__ __launch_bounds__(64) void mfma_selfcheck_kernel(const float *__restr
     }
     if (bad) atomicAdd(mismatches, bad);
 }
+// int8 arm: what the int8 operand mode of the pre-filter assumes about v_mfma_i32_16x16x64_i8 -- lane l holds row l & 15 of
+// either operand and the same 16 k-slots of both, element r of the result is C[4 (l >> 4) + r][l & 15], the products are
+// exact and the accumulator is added to.  A 16 x 16 x 128 product (two chained k-steps) of asymmetric int8 data on the matrix
+// pipe against integer dot products on the vector ALU (`permuted`: against the TRANSPOSED product -- what a wrong lane map
+// looks like).
+__global__ __launch_bounds__(64) void mfma_selfcheck_i8_kernel(const signed char *__restrict__ A, const signed char *__restrict__ B, int permuted,
+                                                               int *__restrict__ mismatches)
+{
+    const int lane = threadIdx.x, l15 = lane & 15, lq = lane >> 4;
+    i32x4 acc = {0, 0, 0, 0};
+    for (int s = 0; s < 2; ++s)
+        acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*reinterpret_cast<const i32x4 *>(A + l15 * 128 + 64 * s + 16 * lq),
+                                                    *reinterpret_cast<const i32x4 *>(B + l15 * 128 + 64 * s + 16 * lq), acc, 0, 0, 0);
+    int bad = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = permuted ? l15 : 4 * lq + r, j = permuted ? 4 * lq + r : l15;
+        int ref = 0;
+        for (int k = 0; k < 128; ++k) ref += (int)A[i * 128 + k] * (int)B[j * 128 + k];
+        bad += ref != acc[r] ? 1 : 0;
+    }
+    if (bad) atomicAdd(mismatches, bad);
+}
+// test hook of the int8 operand mode: the ring values d~^2 - b_q of every (query, clip), computed by the device functions
+// score_mfma_kernel uses, tile by tile from clip 0 (16-clip tiles regardless of video boundaries, the last one partial)
+__global__ __launch_bounds__(64) void score_i8_debug_kernel(const signed char *__restrict__ ql, const signed char *__restrict__ vl,
+                                                            const float *__restrict__ qf, const float *__restrict__ va, int64_t Nq,
+                                                            int total_clips, float *__restrict__ out)
+{
+    const int lane = threadIdx.x, j = lane & 15, g = lane >> 4, group = blockIdx.x;
+    const int c_tile = blockIdx.y * 16;
+    i32x4 Ai[4][3][2], B0[3], B1[3], cls[4][4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        int64_t row = (int64_t)group * 64 + 16 * t + j;
+        row = row < Nq ? row : Nq - 1;
+#pragma unroll
+        for (int l = 0; l < 3; ++l) { Ai[t][l][0] = i8_load(ql, row, l, 0, g); Ai[t][l][1] = i8_load(ql, row, l, 1, g); }
+    }
+    const int64_t last_row = (int64_t)total_clips - 1;
+    const int64_t row = c_tile + j < last_row ? c_tile + j : last_row;
+#pragma unroll
+    for (int l = 0; l < 3; ++l) { B0[l] = i8_load(vl, row, l, 0, g); B1[l] = i8_load(vl, row, l, 1, g); }
+    i8_tile_mfma<0, 4>(Ai, B0, 0, cls);
+    i8_tile_mfma<0, 4>(Ai, B1, 1, cls);
+    const float f = qf[group], ac = va[row];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const f32x4 o = i8_combine(cls[t], f, ac);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t q = (int64_t)group * 64 + 16 * t + 4 * g + i;
+            if (q < Nq && c_tile + j < total_clips) out[q * total_clips + c_tile + j] = o[i];
+        }
+    }
+}
 static int run_smallq(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv,
                       int total_clips, int max_clips, int D, float eps, int64_t id_base, int k, float *out_dist, int64_t *out_idx, int num_rank,
                       const float *rank_dist, const int64_t *rank_idx, int64_t *count_lt, void *workspace, vfr_stream_t stream)
@@ -2543,6 +2623,59 @@ extern "C" int vfr_mfma_selfcheck(const float *A, const float *B, int K, int rev
     if (hipMemsetAsync(mismatches, 0, sizeof(int), st) != hipSuccess) return vfr::fail(VFR_EHIP, "vfr_mfma_selfcheck: hipMemsetAsync failed");
     hipLaunchKernelGGL(vfr::mfma_selfcheck_kernel, dim3(1), dim3(64), 0, st, A, B, K, reversed, mismatches);
     VFR_CHECK_LAUNCH("mfma_selfcheck_kernel");
+    return VFR_OK;
+}
+
+extern "C" int vfr_mfma_selfcheck_i8(const int8_t *A, const int8_t *B, int permuted, int *mismatches, vfr_stream_t stream)
+{
+    VFR_REQUIRE(A && B && mismatches && ((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0, VFR_EINVAL, "vfr_mfma_selfcheck_i8: bad argument (16-byte aligned A, B)");
+    hipStream_t st = vfr::as_stream(stream);
+    if (hipMemsetAsync(mismatches, 0, sizeof(int), st) != hipSuccess) return vfr::fail(VFR_EHIP, "vfr_mfma_selfcheck_i8: hipMemsetAsync failed");
+    hipLaunchKernelGGL(vfr::mfma_selfcheck_i8_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const signed char *>(A),
+                       reinterpret_cast<const signed char *>(B), permuted, mismatches);
+    VFR_CHECK_LAUNCH("mfma_selfcheck_i8_kernel");
+    return VFR_OK;
+}
+
+extern "C" int vfr_score_i8_debug(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, int Nv, int total_clips, int D,
+                                  float eps, void *workspace, size_t workspace_bytes, int8_t *vlimbs, int8_t *qlimbs, double *bank_const,
+                                  double *query_const, double *query_scale, float *query_factor, float *qmeta, float *va, float *mu,
+                                  float *ring, vfr_stream_t stream)
+{
+    VFR_REQUIRE(Q && V && clip_offsets && Nq > 0 && Nv > 0 && total_clips > 0 && D == vfr::FAST_D, VFR_EINVAL, "vfr_score_i8_debug: bad argument (D = 100)");
+    VFR_REQUIRE(vlimbs && qlimbs && bank_const && query_const && query_scale && query_factor && qmeta && va && mu && ring, VFR_EINVAL,
+                "vfr_score_i8_debug: null output");
+    VFR_REQUIRE(workspace && workspace_bytes >= vfr_score_topk_mfma_workspace_bytes(Nq, Nv, total_clips, 0), VFR_EWORKSPACE,
+                "vfr_score_i8_debug: workspace %zu < %zu bytes", workspace_bytes, vfr_score_topk_mfma_workspace_bytes(Nq, Nv, total_clips, 0));
+    hipStream_t st = vfr::as_stream(stream);
+    vfr::MfmaWs mw = vfr::carve_mfma(workspace, Nq, Nv, total_clips, 0);
+    if (int rc = vfr::fill_region(mw.zero_base, 0u, mw.zero_bytes, st)) return rc;
+    vfr::BankSig now{};
+    now.total_clips = total_clips; now.Nv = Nv; now.D = D; now.eps_bits = __builtin_bit_cast(unsigned, eps); now.has_i8 = 1;
+    const int64_t nwords = (int64_t)total_clips * D;
+    int hb = (int)vfr::cdiv(nwords, 256 * 4 * 8);
+    hb = hb < 1 ? 1 : (hb > 2048 ? 2048 : hb);
+    const int groups = (int)vfr::cdiv(Nq, 64);
+    hipLaunchKernelGGL(vfr::mfma_bank_hash_kernel, dim3((unsigned)hb), dim3(256), 0, st, reinterpret_cast<const unsigned *>(V), nwords,
+                       reinterpret_cast<const unsigned *>(clip_offsets), (int64_t)Nv + 1, mw.hash_now);
+    hipLaunchKernelGGL(vfr::mfma_bank_check_kernel, dim3(1), dim3(1), 0, st, mw.hash_now, now, 0, mw.sig, mw.stale, mw.rv, mw.bankc);
+    hipLaunchKernelGGL(vfr::mfma_mean_partial_kernel, dim3((unsigned)mw.mean_blocks), dim3(1024), 0, st, V, total_clips, D, mw.mean_rows,
+                       mw.mean_partial, mw.stale, mw.mean_minmax);
+    hipLaunchKernelGGL(vfr::mfma_mean_final_kernel, dim3(1), dim3(1024), 0, st, mw.mean_partial, mw.mean_blocks, D, total_clips, mw.mu, mw.stale,
+                       mw.mean_minmax, mw.bankc);
+    hipLaunchKernelGGL(vfr::mfma_prep_v_i8_kernel, dim3((unsigned)vfr::cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps, mw.mu,
+                       mw.vl, mw.va, mw.rv, mw.bankc, mw.stale);
+    hipLaunchKernelGGL(vfr::mfma_prep_q_i8_kernel, dim3((unsigned)groups), dim3(1024), 0, st, Q, Nq, D, eps, mw.mu, mw.ql, mw.rv, mw.bankc, 0,
+                       (const float *)nullptr, mw.qmeta, mw.qf, mw.qdbg, mw.qscale);
+    hipLaunchKernelGGL(vfr::score_i8_debug_kernel, dim3((unsigned)groups, (unsigned)vfr::cdiv(total_clips, 16)), dim3(64), 0, st, mw.ql, mw.vl,
+                       mw.qf, mw.va, Nq, total_clips, ring);
+    VFR_CHECK_LAUNCH("vfr_score_i8_debug");
+    const struct { void *dst; const void *src; size_t bytes; } cp[] = {
+        {vlimbs, mw.vl, (size_t)total_clips * vfr::I8_ROW}, {qlimbs, mw.ql, (size_t)Nq * vfr::I8_ROW}, {bank_const, mw.bankc, vfr::I8C_COUNT * 8},
+        {query_const, mw.qdbg, (size_t)Nq * 16}, {query_scale, mw.qscale, (size_t)groups * 8}, {query_factor, mw.qf, (size_t)groups * 4},
+        {qmeta, mw.qmeta, (size_t)Nq * 16}, {va, mw.va, (size_t)total_clips * 4}, {mu, mw.mu, 128 * 4}};
+    for (const auto &c : cp)
+        if (hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return vfr::fail(VFR_EHIP, "vfr_score_i8_debug: copy failed");
     return VFR_OK;
 }
 

@@ -38,6 +38,29 @@
 // dfl = 3/4 of the smaller rank-key distance of the query (per-query constant); for the top-k check the floor is the best
 // approximate score itself (no clip is closer to the query than the best single-clip moment).
 //
+// int8 limbs (option "score_i8": the operand mode of the f32 path above; margins, marking, top-k and fallback unchanged).
+// The fp32 GEMM only feeds decisions, and fp32 is the matrix pipe's slowest format; int8 x int8 products accumulated in int32
+// are EXACT and order-independent by the definition of v_mfma_i32_16x16x64_i8, so the only approximation left is the
+// quantisation of the operands, whose size is computed.  Centred rows x (the values above) become integers
+// X = rint(x s) in fp64, |X| <= 127 (65536 + 256 + 1), stored as three balanced base-256 digits in [-128, 127] (one int8
+// plane per digit, K padded to 128 with zeros); s_v = XMAX / max |v_k - mu_k| for the bank (from per-column extremes gathered in
+// the mean pass), s_q likewise per 64-query group.  With x^ = X / s:
+//     d~^2 - b_q = a_c - 2 v^.q^,      s_q s_v v^.q^ = sum_w 256^w C_w,   C_w = sum over limb pairs a + b = w, and k, of the digit products
+//   * quantisation: v.q - v^.q^ = (v - v^).q + v^.(q - q^), so 2 |v.q - v^.q^| <= 2 (eps_v |q|_1 + eps_q max_c |v^_c|_1) with the ACHIEVED
+//     eps_v = max |v - v^| over the bank, eps_q = max |q - q^| of the query, |q|_1 of the centred query and the bank's largest
+//     |X_v|_1 / s_v -- all computed in fp64 by the pre-passes;
+//   * class 0 (low digit x low digit) is not computed: |C_0| <= D 2^14, i.e. 2 D 2^14 / (s_q s_v) =: Edrop;
+//   * combine (i8_combine): t = C_1; t = fma(C_2, 2^8, t); t = fma(C_3, 2^16, t); t = fma(C_4, 2^24, t); o = fma(t, f, a_c),
+//     f = fl(-512 / (s_q s_v)).  |C_w| <= 3 D 2^14 < 2^23: the conversions are exact.  The first two fmas round numbers bounded by
+//     B2 = D 2^14 (2 + 3 * 256) and B3 = B2 + 2^16 * 2 D 2^14: u (B2 + B3) |f| ("early" term, ~1.6 u max|q_k| max|v_k|);
+//     the third fma and the rounding of f each cost u |f t| <= u (2 |v^.q^| + Edrop) <= u (2 R^ q^ + Edrop),
+//     R^ = R + eps_v sqrt(D), q^ = |q| + eps_q sqrt(D) (norms of the quantised rows);
+//   * the last fma, the fp64 -> fp32 roundings of a_c and b_q and the kernel's add of b_q: 4 u G^,
+//     G^ = (R^ + q^)^2 + 2 eps sqrt(D) (R^ + q^) + D eps^2 + Edrop bounding every one of those results.
+//   E2 := the sum of these terms (1 % head-room on the rounding terms, evaluated in fp64, rounded up) -- about 6-9 u G where
+//   the fp32 mode takes 20 u G; a bank with one huge centred element has a coarse s_v: eps_v, hence E2, grows with it, more pairs
+//   are re-scored or fall back, results stay exact (tests/test_score_i8_gpu.py).  Everything downstream reads E2 from qmeta.z.
+//
 // bf16 mode (BASELINE config 5): operands rounded to bf16, fp32 accumulate (v_mfma_f32_16x16x32_bf16), a_c / b_q from the
 // fp32 data.  Approximate by design: rank counts use the approximate distances as they are, the top-k is the exact re-rank
 // of the k' best bf16 candidates.  No margins, no queue, no fallback.
@@ -50,6 +73,11 @@ constexpr int MF_HBINS = 32;                 // bins of the top-k threshold hist
 constexpr int MF_TAB = 4;                    // table words per (query, key, L): LO, HI (exact, exclusive bit bounds), LO wide, width
 #define MF_RING_ROWS(NT) ((NT) > 6 ? 38 : 32)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+// int8 operand mode (see "int8 limbs" above)
+constexpr int I8_XMAX = 127 * 65536 + 127 * 256 + 127;   // |X| <= I8_XMAX <=> three balanced base-256 digits in [-128, 127] hold X
+constexpr int I8_ROW = 3 * 128;              // bytes per row: [limb][k], K padded from 100 to 128 with zeros
+enum { I8C_SV = 0, I8C_EPSV = 1, I8C_L1V = 2, I8C_VMAX = 3, I8C_COUNT = 4 };   // bank constants (fp64): scale, max |v - X/s|, max |X|_1 / s, max |v_k - mu_k|
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct MfmaArgs {
@@ -64,6 +92,8 @@ struct MfmaArgs {
     const unsigned short *vb;                // bf16 mode: V as bf16 [total_clips][128] (zero padded)
     const float *rv;                         // [1] max norm of the CENTRED clip rows (pre-pass)
     const float *vc, *qc;                    // V - mu [total_clips, D], Q - mu [Nq, D]: the operands of the approximate GEMM
+    const signed char *vl, *ql;              // int8 mode: the same rows as limb planes [row][3][128]
+    const float *qf;                         // int8 mode: [groups] -2 * 256 / (s_q s_v), the factor of the combined class sums
     unsigned *qbound;                        // [Nq][2] whole-video bounds of the rank keys (zeroed per call, atomicMax by the table pre-pass):
                                              //   [0] bits of HAB: dmin >= HAB => no moment of the video is counted or ambiguous, for either key
                                              //   [1] ~bits of BBL: dmax <  BBL => every moment of the video is counted, for both keys
@@ -82,12 +112,14 @@ struct MfmaArgs {
 // only as good as the bank they were computed from.  Every pre-filter call hashes what the products depend on -- every
 // 32-bit word of V (each multiplied by an odd weight derived from its position, summed modulo 2^64: order-independent, so
 // the block partials can be added with atomics) and of the clip offsets -- and a one-thread kernel compares
-// {hash, total_clips, Nv, D, eps, bf16 copy present} with the signature the previous call left behind the products:
+// {hash, total_clips, Nv, D, eps, bf16 copy present, centred rows as int8 limbs} with the signature the previous call left behind the products:
 //   * BANK_READY and equal      -> `stale` = 0: the bank pre-passes, which are always launched, return at once;
 //   * anything else             -> `stale` = 1: they recompute, and the new signature is stored.
 // No host decision, no synchronisation; 84 MB of V hash in ~20 us.  What is NOT covered: the caller's promise that the
 // product region of the workspace itself was not overwritten since that call.
-struct BankSig { unsigned long long hash; int total_clips, Nv, D; unsigned eps_bits; int has_bf16; int pad; };
+// has_i8: the centred rows are stored as int8 limb planes (with the bank constants of the int8 pre-filter) INSTEAD of the fp32
+// copy -- the two share one region of the workspace, so the stored and the wanted form must be equal, not merely present
+struct BankSig { unsigned long long hash; int total_clips, Nv, D; unsigned eps_bits; int has_bf16; int has_i8; };
 __global__ __launch_bounds__(256) void mfma_bank_hash_kernel(const unsigned *__restrict__ Vw, int64_t nwords,
                                                              const unsigned *__restrict__ off_w, int64_t noff,
                                                              unsigned long long *__restrict__ hash)
@@ -114,56 +146,96 @@ __global__ __launch_bounds__(256) void mfma_bank_hash_kernel(const unsigned *__r
     if (threadIdx.x == 0) atomicAdd(hash, red[0] + red[1] + red[2] + red[3]);
 }
 __global__ void mfma_bank_check_kernel(const unsigned long long *__restrict__ hash_now, BankSig now, int ready_claimed,
-                                       BankSig *__restrict__ stored, int *__restrict__ stale, float *__restrict__ rv)
+                                       BankSig *__restrict__ stored, int *__restrict__ stale, float *__restrict__ rv,
+                                       double *__restrict__ bankc = nullptr)
 {
     now.hash = *hash_now;
     const BankSig old = *stored;
     const bool same = ready_claimed && old.hash == now.hash && old.total_clips == now.total_clips && old.Nv == now.Nv && old.D == now.D &&
-                      old.eps_bits == now.eps_bits && old.has_bf16 >= now.has_bf16;
+                      old.eps_bits == now.eps_bits && old.has_bf16 >= now.has_bf16 && old.has_i8 == now.has_i8;
     *stale = same ? 0 : 1;
     if (!same) { *stored = now; *rv = 0.0f; }                             // (rv: the max-norm accumulator of mfma_prep_v_kernel)
+    if (!same && bankc) { bankc[I8C_EPSV] = 0.0; bankc[I8C_L1V] = 0.0; }  // (the max accumulators of mfma_prep_v_i8_kernel)
 }
 
 
 // mean clip embedding mu [D] (D <= 128), two deterministic stages: 1024-thread blocks sum a slice of rows (thread = column x
 // row phase, fp64), then one 1024-thread block adds the per-block partials (8 slices per column)
 __global__ __launch_bounds__(1024) void mfma_mean_partial_kernel(const float *__restrict__ V, int total_clips, int D, int rows_per_block,
-                                                                 double *__restrict__ partial, const int *__restrict__ stale)
+                                                                 double *__restrict__ partial, const int *__restrict__ stale,
+                                                                 float2 *__restrict__ minmax = nullptr)
 {
     __shared__ double red[1024];
+    __shared__ float2 mm[1024];
     if (!*stale) return;                                                  // the products in the workspace are this bank's
     const int k = threadIdx.x & 127, ph = threadIdx.x >> 7;              // column, row phase (8)
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
     int64_t r1 = r0 + rows_per_block;
     r1 = r1 < total_clips ? r1 : total_clips;
     double acc = 0.0;
+    float mn = __builtin_inff(), mx = -__builtin_inff();                  // per-column extremes (int8 pre-filter: the bank's scale) -- the same pass
     if (k < D)
-        for (int64_t r = r0 + ph; r < r1; r += 8) acc += V[r * D + k];
+        for (int64_t r = r0 + ph; r < r1; r += 8) {
+            const float x = V[r * D + k];
+            acc += x;
+            mn = x < mn ? x : mn; mx = x > mx ? x : mx;
+        }
     red[threadIdx.x] = acc;
+    mm[threadIdx.x] = make_float2(mn, mx);
     __syncthreads();
     if (ph == 0 && k < D) {
         double t = 0.0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) t += red[i * 128 + k];
         partial[(int64_t)blockIdx.x * D + k] = t;
+        if (minmax) {
+#pragma unroll
+            for (int i = 1; i < 8; ++i) { const float2 o = mm[i * 128 + k]; mn = o.x < mn ? o.x : mn; mx = o.y > mx ? o.y : mx; }
+            minmax[(int64_t)blockIdx.x * D + k] = make_float2(mn, mx);
+        }
     }
 }
 __global__ __launch_bounds__(1024) void mfma_mean_final_kernel(const double *__restrict__ partial, int nblocks, int D, int total_clips,
-                                                               float *__restrict__ mu, const int *__restrict__ stale)
+                                                               float *__restrict__ mu, const int *__restrict__ stale,
+                                                               const float2 *__restrict__ minmax = nullptr, double *__restrict__ bankc = nullptr)
 {
     __shared__ double red[1024];
+    __shared__ float2 mm[1024];
+    __shared__ float cmax[128];
     if (!*stale) return;
     const int k = threadIdx.x & 127, sl = threadIdx.x >> 7;
     double acc = 0.0;
+    float mn = __builtin_inff(), mx = -__builtin_inff();
     if (k < D)
-        for (int b = sl; b < nblocks; b += 8) acc += partial[(int64_t)b * D + k];
+        for (int b = sl; b < nblocks; b += 8) {
+            acc += partial[(int64_t)b * D + k];
+            if (minmax) { const float2 o = minmax[(int64_t)b * D + k]; mn = o.x < mn ? o.x : mn; mx = o.y > mx ? o.y : mx; }
+        }
     red[threadIdx.x] = acc;
+    mm[threadIdx.x] = make_float2(mn, mx);
     __syncthreads();
-    if (sl == 0 && k < D) {
-        double t = 0.0;
+    if (sl == 0) {
+        float c = 0.0f;
+        if (k < D) {
+            double t = 0.0;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) t += red[i * 128 + k];
-        mu[k] = (float)(t / (double)(total_clips > 0 ? total_clips : 1));
+            for (int i = 0; i < 8; ++i) t += red[i * 128 + k];
+            const float m_ = (float)(t / (double)(total_clips > 0 ? total_clips : 1));
+            mu[k] = m_;
+#pragma unroll
+            for (int i = 1; i < 8; ++i) { const float2 o = mm[i * 128 + k]; mn = o.x < mn ? o.x : mn; mx = o.y > mx ? o.y : mx; }
+            // rounding is monotonic: the largest |fl(v_k - mu_k)| of the column is taken at one of its extremes
+            const float a0 = __builtin_fabsf(mx - m_), a1 = __builtin_fabsf(mn - m_);
+            c = (minmax && total_clips > 0) ? (a0 > a1 ? a0 : a1) : 0.0f;
+        }
+        cmax[k] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && bankc) {
+        float vmax = 0.0f;
+        for (int i = 0; i < 128; ++i) vmax = cmax[i] > vmax ? cmax[i] : vmax;
+        bankc[I8C_VMAX] = (double)vmax;
+        bankc[I8C_SV] = vmax > 0.0f ? (double)I8_XMAX / (double)vmax : 1.0;
     }
 }
 
@@ -236,6 +308,164 @@ __global__ __launch_bounds__(256) void mfma_prep_q_kernel(const float *__restric
     for (int r = 0; r < NR; ++r) { const float x = rank_dist[r * Nq + q]; xmin = x < xmin ? x : xmin; }
     const float dfl = NR > 0 && xmin < __builtin_inff() ? 0.75f * xmin : 0.0f;
     qmeta[q] = make_float4(bq, dfl, E2, rs);
+}
+
+// ---- int8 limbs: the pre-passes of the int8 operand mode ----
+// X = rint(x * s) (fp64, |X| <= I8_XMAX) as three balanced base-256 digits d0 + 256 d1 + 65536 d2, each in [-128, 127]
+__device__ __forceinline__ int i8_quantise(double x, double s)
+{
+    double y = __builtin_rint(x * s);
+    y = y > (double)I8_XMAX ? (double)I8_XMAX : (y < -(double)I8_XMAX ? -(double)I8_XMAX : y);
+    return (int)y;
+}
+__device__ __forceinline__ void i8_digits(int X, signed char *d)
+{
+    const int d0 = ((X + 128) & 255) - 128;                               // (two's complement: & 255 is the floor modulus)
+    const int X1 = (X - d0) >> 8;                                         // exact: X - d0 is a multiple of 256
+    const int d1 = ((X1 + 128) & 255) - 128;
+    const int d2 = (X1 - d1) >> 8;                                        // |X| <= I8_XMAX keeps it in [-128, 127]
+    d[0] = (signed char)d0; d[1] = (signed char)d1; d[2] = (signed char)d2;
+}
+__device__ __forceinline__ void atomic_max_pos_double(double *p, double x)   // x >= 0: the bit patterns order like the values
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    // (one contended atomic per row would serialise the launch: only rows that can raise the maximum issue one)
+    if (b > __hip_atomic_load(reinterpret_cast<unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        atomicMax(reinterpret_cast<unsigned long long *>(p), b);
+}
+// mfma_prep_v_kernel for the int8 mode: the same a_c and largest centred norm (same arithmetic, same order); the centred row goes
+// out as limb planes instead of the fp32 copy, and the bank's achieved quantisation error and largest |X|_1 / s are collected
+// (maxima: order-independent)
+__global__ __launch_bounds__(256) void mfma_prep_v_i8_kernel(const float *__restrict__ V, int total_clips, int D, float eps,
+                                                             const float *__restrict__ mu, signed char *__restrict__ vl,
+                                                             float *__restrict__ va, float *__restrict__ rv,
+                                                             double *__restrict__ bankc, const int *__restrict__ stale)
+{
+    if (!*stale) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= total_clips) return;
+    const float *v = V + row * D;
+    const double sv = bankc[I8C_SV];
+    double s2 = 0.0, s1 = 0.0, err = 0.0;
+    long long l1 = 0;
+    for (int k = lane; k < 128; k += 64) {
+        signed char d[3] = {0, 0, 0};
+        if (k < D) {
+            const float c = v[k] - mu[k];
+            const double x = c;
+            s2 += x * x; s1 += x;
+            const int X = i8_quantise(x, sv);
+            const double e = __builtin_fabs(x - (double)X / sv);
+            err = e > err ? e : err;
+            l1 += X < 0 ? -(long long)X : (long long)X;
+            i8_digits(X, d);
+        }
+#pragma unroll
+        for (int l = 0; l < 3; ++l) vl[row * I8_ROW + l * 128 + k] = d[l];
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        s2 += __shfl_xor(s2, o, 64); s1 += __shfl_xor(s1, o, 64);
+        const double e = __shfl_xor(err, o, 64);
+        err = e > err ? e : err;
+        l1 += __shfl_xor(l1, o, 64);
+    }
+    if (lane == 0) {
+        va[row] = (float)(s2 + 2.0 * (double)eps * s1 + (double)D * (double)eps * (double)eps);
+        const unsigned nb = __float_as_uint((float)__builtin_sqrt(s2) * 1.0000002f);
+        if (nb > __hip_atomic_load(reinterpret_cast<unsigned *>(rv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            atomicMax(reinterpret_cast<unsigned *>(rv), nb);
+        atomic_max_pos_double(bankc + I8C_EPSV, err * (1.0 + 1e-12));     // (the fp64 roundings of x - X / s itself)
+        atomic_max_pos_double(bankc + I8C_L1V, (double)l1 / sv * (1.0 + 1e-12));
+    }
+}
+
+// mfma_prep_q_kernel for the int8 mode: one block per 64-query group (16 lanes per query).  The query scale is per GROUP: the
+// factor -2 / (s_q s_v) is then uniform over the wave that scores the group -- one scalar in score_mfma_kernel, where a
+// per-query scale would cost one register per accumulator element (16) in a kernel that has none -- and the group's queries
+// are neighbours in difficulty order with norms of one magnitude; a global scale would need a pass of its own for the maximum.
+// b_q, dfl and qmeta.w as in mfma_prep_q_kernel; E2 from the computed constants ("int8 limbs" in the header).
+// qdbg [Nq] = {|q - mu|_1, achieved max |x - X / s_q| of the query}, qscale [groups] = s_q: what the bound was built from.
+__global__ __launch_bounds__(1024) void mfma_prep_q_i8_kernel(const float *__restrict__ Q, int64_t Nq, int D, float eps,
+                                                              const float *__restrict__ mu, signed char *__restrict__ ql,
+                                                              const float *__restrict__ rv, const double *__restrict__ bankc, int NR,
+                                                              const float *__restrict__ rank_dist, float4 *__restrict__ qmeta,
+                                                              float *__restrict__ qf, double2 *__restrict__ qdbg,
+                                                              double *__restrict__ qscale)
+{
+    __shared__ float gmax[64];
+    const int sub = threadIdx.x & 15, ql_ = threadIdx.x >> 4;
+    const int64_t q = (int64_t)blockIdx.x * 64 + ql_;
+    const bool on = q < Nq;
+    const float *p = Q + (on ? q : 0) * D;
+    float c[8];
+    double s2 = 0.0, s1 = 0.0, l1 = 0.0;
+    float amax = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int k = sub + 16 * i;
+        c[i] = (on && k < D) ? p[k] - mu[k] : 0.0f;
+        const double x = c[i];
+        if (on && k < D) { s2 += x * x; s1 += x; }                        // (the order of mfma_prep_q_kernel's loop)
+        l1 += __builtin_fabs(x);
+        amax = __builtin_fabsf(c[i]) > amax ? __builtin_fabsf(c[i]) : amax;
+    }
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) {
+        s2 += __shfl_xor(s2, o, 64); s1 += __shfl_xor(s1, o, 64); l1 += __shfl_xor(l1, o, 64);
+        const float a = __shfl_xor(amax, o, 64);
+        amax = a > amax ? a : amax;
+    }
+    if (sub == 0) gmax[ql_] = amax;
+    __syncthreads();
+    float qmax = 0.0f;
+    for (int i = 0; i < 64; ++i) qmax = gmax[i] > qmax ? gmax[i] : qmax;
+    const double sq = qmax > 0.0f ? (double)I8_XMAX / (double)qmax : 1.0;
+    double err = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int k = sub + 16 * i;
+        const double x = c[i];
+        const int X = i8_quantise(x, sq);
+        const double e = __builtin_fabs(x - (double)X / sq);
+        err = e > err ? e : err;
+        signed char d[3];
+        i8_digits(X, d);
+        if (on) {
+#pragma unroll
+            for (int l = 0; l < 3; ++l) ql[q * I8_ROW + l * 128 + k] = d[l];
+        }
+    }
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) { const double e = __shfl_xor(err, o, 64); err = e > err ? e : err; }
+    const double sv = bankc[I8C_SV];
+    const double W = 1.0 / (sq * sv);
+    if (threadIdx.x == 0) { qf[blockIdx.x] = (float)(-512.0 * W); qscale[blockIdx.x] = sq; }
+    if (!on || sub != 0) return;
+    err *= 1.0 + 1e-12;
+    const float bq = (float)(s2 - 2.0 * (double)eps * s1);
+    const float qn = (float)__builtin_sqrt(s2) * 1.0000002f;
+    const float R = *rv;
+    const float rs = (R + qn) * 1.000001f;
+    // ---- E2 ("int8 limbs" in the header), fp64, rounded up ----
+    const double u = (double)MF_U, Dd = (double)D, sD = __builtin_sqrt(Dd), e64 = (double)eps;
+    const double epsv = bankc[I8C_EPSV], l1v = bankc[I8C_L1V];
+    const double Equant = 2.0 * (epsv * l1 + err * l1v);
+    const double Edrop = 2.0 * Dd * 16384.0 * W;
+    const double B2 = Dd * 16384.0 * 770.0, B3 = B2 * 1.000001 + 65536.0 * 2.0 * Dd * 16384.0;
+    const double Eearly = u * 512.0 * W * (B2 + B3) * 1.01;
+    const double Rh = (double)R + epsv * sD, qh = (double)qn + err * sD;
+    const double cross = 2.0 * Rh * qh + Edrop;
+    const double Et = 2.0 * u * cross * 1.01;
+    const double Gp = (Rh + qh) * (Rh + qh) + 2.0 * e64 * sD * (Rh + qh) + Dd * e64 * e64 + Edrop;
+    const double Efin = 4.0 * u * Gp * 1.01;
+    const float E2 = (float)((Equant + Edrop + Eearly + Et + Efin) * 1.0001);
+    float xmin = __builtin_inff();
+    for (int r = 0; r < NR; ++r) { const float x = rank_dist[r * Nq + q]; xmin = x < xmin ? x : xmin; }
+    const float dfl = NR > 0 && xmin < __builtin_inff() ? 0.75f * xmin : 0.0f;
+    qmeta[q] = make_float4(bq, dfl, E2, rs);
+    qdbg[q] = make_double2(l1, err);
 }
 
 // one thread per (query, rank key, span length): the exact bit bounds of the sum and their widened forms
@@ -395,11 +625,55 @@ __global__ __launch_bounds__(256) void mfma_scatter_results_kernel(const int *__
 
 // ---------------------------------------------------------------------------------------------------------------------
 // approximate fused kernel.  thread = query for the moment triangle (as score_fast_kernel); the distances of 16-clip
-// column tiles x the wave's 64 queries come from 100 (f32) / 16 (bf16) MFMAs per tile, the accumulator tiles go through a
+// column tiles x the wave's 64 queries come from 100 (f32) / 16 (bf16) / 64 (int8 limbs) MFMAs per tile, the accumulator tiles go through a
 // per-wave LDS ring (clip-major rows of 64 queries, 16-byte chunks XOR-swizzled by row so that both the b128 tile writes
 // and the per-query reads are bank-conflict free) and a video is processed as soon as its last clip has been written.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NT, int KPL, int NR, bool TOPK, bool BF16>
+// int8 tile: 64 queries x 16 clips.  A[t][limb][k-step] / B[limb] (k-step 0), B1[limb] (k-step 1): 16 bytes per lane and
+// (limb, k-step) -- bytes 64 s + 16 g .. + 15 of the row's limb plane, the SAME k-slots on both sides, so the product does not
+// depend on how the instruction numbers k inside a lane.  Per class w = a + b of limb pairs (weight 256^w) one int32
+// accumulator chained over the class's pairs and both k-steps; class 0 (low limb x low limb) is not computed -- its worst
+// case is in E2.  |class sum| <= pairs * K * 128 * 128 = 3 * 100 * 2^14 < 2^23: v_cvt_f32_i32 is exact.  Combine, per element,
+// least significant first:  t = C1;  t = fma(C2, 2^8, t);  t = fma(C3, 2^16, t);  t = fma(C4, 2^24, t);  o = fma(t, f, a_c)
+// with f = fl(-2 * 256 / (s_q s_v)): the first two fmas round integers below 2^38 (their error is the "early" term of E2),
+// the roundings that matter are the last two.
+// (query tiles T0 .. T1 - 1: score_mfma_kernel runs the tile in two halves -- 16 accumulators of 4 registers would not fit
+// beside the 96 registers of A)
+template <int T0, int T1>
+__device__ __forceinline__ void i8_tile_mfma(const i32x4 (&A)[4][3][2], const i32x4 (&B)[3], int s, i32x4 (&cls)[4][4])
+{
+#pragma unroll
+    for (int t = T0; t < T1; ++t)
+#pragma unroll
+        for (int w = 1; w <= 4; ++w)
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const int b = w - a;
+                if (b < 0 || b > 2) continue;
+                const bool first = s == 0 && a == (w > 2 ? w - 2 : 0);    // the class's first pair starts from zero
+                cls[t][w - 1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t][a][s], B[b], first ? i32x4{0, 0, 0, 0} : cls[t][w - 1], 0, 0, 0);
+            }
+}
+__device__ __forceinline__ f32x4 i8_combine(const i32x4 (&c)[4], float f, float ac)
+{
+    f32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float t = (float)c[0][i];
+        t = __builtin_fmaf((float)c[1][i], 256.0f, t);
+        t = __builtin_fmaf((float)c[2][i], 65536.0f, t);
+        t = __builtin_fmaf((float)c[3][i], 16777216.0f, t);
+        o[i] = __builtin_fmaf(t, f, ac);
+    }
+    return o;
+}
+__device__ __forceinline__ i32x4 i8_load(const signed char *rows, int64_t row, int limb, int s, int g)
+{
+    return *reinterpret_cast<const i32x4 *>(rows + row * I8_ROW + limb * 128 + 64 * s + 16 * g);
+}
+
+// OPM: operand mode of the approximate GEMM -- 0: fp32, 1: bf16 (approximate by design), 2: int8 limbs
+template <int NT, int KPL, int NR, bool TOPK, int OPM>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8)))
 void score_mfma_kernel(const float *__restrict__ Qp, const float *__restrict__ Vp, const int32_t *__restrict__ clip_off,
                        const int64_t *__restrict__ mom_off, ScoreArgs a, MfmaArgs m)
@@ -409,7 +683,8 @@ void score_mfma_kernel(const float *__restrict__ Qp, const float *__restrict__ V
     // enough; 38 rows (9.5 KB) + the 10.5 KB bound table = 20 KB per wave = eight waves per CU (48 rows left room for seven:
     // one SIMD of every CU ran a single wave with nothing to cover its operand latency)
     constexpr int CAP = KPL * 64, RR = MF_RING_ROWS(NT), NRR = NR > 0 ? NR : 1, NW = (NT + 2) / 3;
-    constexpr int KS = BF16 ? 4 : 25;                                   // MFMA k-steps per tile
+    constexpr bool BF16 = OPM == 1, I8 = OPM == 2;
+    constexpr int KS = BF16 ? 4 : 25;                                   // MFMA k-steps per tile (f32 / bf16)
     const int lane = threadIdx.x, j = lane & 15, g = lane >> 4;
     const int task = blockIdx.x;
     const int chunk = task / a.num_groups, group = task - chunk * a.num_groups;
@@ -426,14 +701,19 @@ void score_mfma_kernel(const float *__restrict__ Qp, const float *__restrict__ V
     const float bq = meta.x, dfl = (active && !BF16) ? meta.y : 0.0f;
 
     // ---- A operand: -2 q, queries 16t + j of the group, k-slots of this lane's quarter g ----
-    float Af[BF16 ? 1 : 4][BF16 ? 1 : 25];
+    float Af[OPM == 0 ? 4 : 1][OPM == 0 ? 25 : 1];
     bf16x8 Ab[BF16 ? 4 : 1][BF16 ? 4 : 1];
+    i32x4 Ai[I8 ? 4 : 1][3][2];
+    const float qfac = I8 ? m.qf[group] : 0.0f;                           // wave-uniform
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         int64_t row = (int64_t)group * 64 + 16 * t + j;
         row = row < a.Nq ? row : a.Nq - 1;
         const float *p = m.qc + row * FAST_D;
-        if constexpr (!BF16) {
+        if constexpr (I8) {
+#pragma unroll
+            for (int l = 0; l < 3; ++l) { Ai[t][l][0] = i8_load(m.ql, row, l, 0, g); Ai[t][l][1] = i8_load(m.ql, row, l, 1, g); }
+        } else if constexpr (!BF16) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 const float4 x = *reinterpret_cast<const float4 *>(p + 24 * g + 4 * i);
@@ -536,7 +816,9 @@ void score_mfma_kernel(const float *__restrict__ Qp, const float *__restrict__ V
     // 96 + g).  Only a window of three blocks is held in registers: block b + 3 is requested while block b feeds its 16 MFMAs,
     // the last three requests of a tile are the first three blocks of the NEXT tile, which land under the moment triangles.
     const int64_t last_row = (int64_t)a.total_clips - 1;
-    float4 Bq[BF16 ? 1 : 3];
+    float4 Bq[OPM == 0 ? 3 : 1];
+    i32x4 Bi[3];                                                         // int8: k-step 0 of this / (after its MFMAs) the next tile; k-step 1 is
+                                                                         // requested at the top of the tile and lands under k-step 0's MFMAs
     float Bl = 0.0f, Bl_next = 0.0f;                                     // 25th k-step of this / the next tile
     bf16x8 Bb[BF16 ? 4 : 1];
     float acv_next = 0.0f;
@@ -567,7 +849,12 @@ void score_mfma_kernel(const float *__restrict__ Qp, const float *__restrict__ V
     int v = v0, c_cur = c_lo, c_nxt = clip_off[v0 + 1];
     int64_t m_cur = mom_off[v0];
     if constexpr (BF16) bload_bf16(c_lo);
-    else {
+    else if constexpr (I8) {
+        const int64_t row = brow(c_lo);
+        acv_next = m.va[row];
+#pragma unroll
+        for (int l = 0; l < 3; ++l) Bi[l] = i8_load(m.vl, row, l, 0, g);
+    } else {
         const int64_t row = brow(c_lo);
         acv_next = m.va[row];
         Bl_next = m.vc[row * FAST_D + 96 + g];
@@ -579,7 +866,23 @@ void score_mfma_kernel(const float *__restrict__ Qp, const float *__restrict__ V
         // ---- 64 queries x 16 clips on the matrix cores ----
         f32x4 acc[4];
         const float acv_cur = acv_next;
-        if constexpr (!BF16) {
+        if constexpr (I8) {
+            const int64_t row = brow(c_tile), row_n = brow((int64_t)c_tile + 16);
+            i32x4 B1[3], cls[4][4];
+#pragma unroll
+            for (int l = 0; l < 3; ++l) B1[l] = i8_load(m.vl, row, l, 1, g);
+            i8_tile_mfma<0, 2>(Ai, Bi, 0, cls);
+            i8_tile_mfma<0, 2>(Ai, B1, 1, cls);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) acc[t] = i8_combine(cls[t], qfac, acv_cur);
+            i8_tile_mfma<2, 4>(Ai, Bi, 0, cls);
+#pragma unroll
+            for (int l = 0; l < 3; ++l) Bi[l] = i8_load(m.vl, row_n, l, 0, g);   // the next tile's first half lands under the triangles
+            acv_next = m.va[row_n];
+            i8_tile_mfma<2, 4>(Ai, B1, 1, cls);
+#pragma unroll
+            for (int t = 2; t < 4; ++t) acc[t] = i8_combine(cls[t], qfac, acv_cur);
+        } else if constexpr (!BF16) {
             const int64_t row = brow(c_tile), row_n = brow((int64_t)c_tile + 16);
             Bl = Bl_next;
 #pragma unroll
@@ -626,7 +929,7 @@ void score_mfma_kernel(const float *__restrict__ Qp, const float *__restrict__ V
             wr = wr >= RR ? wr - RR : wr;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const f32x4 o = acc[t] + acv_cur;
+                const f32x4 o = I8 ? acc[t] : acc[t] + acv_cur;               // (int8: a_c went into the combine's last fma)
                 const unsigned off = (unsigned)wr * 256u + ((unsigned)((4 * t + g) ^ j) << 4);
                 *reinterpret_cast<f32x4 *>(reinterpret_cast<char *>(ring) + off) = o;
             }

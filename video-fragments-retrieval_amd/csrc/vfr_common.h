@@ -48,6 +48,7 @@ int opt_mfma_min();
 int opt_score_defer();
 int opt_score_sort();
 int opt_score_hist();
+int opt_score_i8();
 
 // ---- launch-site profiler (vfr_set_option("profile", 1)): HIP events recorded on the launch stream
 // around every instrumented launch; vfr_profile_read() turns them into per-site totals after a sync.
