@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Register / scratch / occupancy table of the kernels in one HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
 
-    python tools/kernel_resources.py video-fragments-retrieval_amd/csrc/score.hip [filter]
+    python tools/kernel_resources.py video-fragments-retrieval_amd/csrc/<unit>.hip [filter]
+
+One unit per call, e.g. the scorer's: score.hip, score_smallq.hip, topk_exchange.hip, video_topk.hip, moment_nms.hip, paragraphs.hip.
 """
 import re
 import subprocess

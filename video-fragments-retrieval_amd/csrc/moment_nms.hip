@@ -1,4 +1,4 @@
-// Diversified moment retrieval (included at the end of score.hip, after video_topk.h: phase 1 IS the video top-k call).
+// Diversified moment retrieval (on top of video_topk.hip: phase 1 IS the video top-k call).
 //
 // Question: the k best MOMENTS of a query, but not k shifted copies of one span of one strong video.  Keys, ids and scores are
 // exactly those of vfr_score_topk_f32: key = (fp32 distance, global moment id) ascending, id = id_base + mom_off[v] + j, j the
@@ -36,7 +36,7 @@
 //             key <= T*, and none can contribute more than min(per_video, k) keys to a top-k).
 //   mnms_topk_kernel   per query: the k smallest keys of its k x P buffer row (radix threshold on the high then the low word,
 //             then a bitonic sort of <= k keys), padded with (+inf, -1)
-#pragma once
+#include "video_topk.h"
 
 namespace vfr {
 

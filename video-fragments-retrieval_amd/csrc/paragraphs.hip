@@ -1,5 +1,5 @@
-// Paragraph-to-video retrieval (included at the end of score.hip, after moment_nms.h: it builds on the video top-k's workspace
-// front, pre-pass, bounds kernel, bound functions and top-k kernel).
+// Paragraph-to-video retrieval (it builds on the video top-k's workspace front, pre-pass, bounds kernel, bound functions and
+// top-k kernel: video_topk.h).
 //
 // Question: which VIDEO does a GROUP of sentences describe?  Q [Nq, D] holds the sentences, a paragraph is a run of consecutive
 // rows given by grp_off [Ng + 1] (non-decreasing from 0 to Nq, runs of at most max_len <= 64 rows).
@@ -37,7 +37,9 @@
 //           video with lo > T cannot be in the top-k.  Every other video is listed (ties at T included).
 //   rank:   hi < own score => counted without a triangle;  lo > own score => not counted;  otherwise listed as undecided and
 //           counted from its exact key (which also settles score == own by the video index).  NaN anywhere lands on "listed".
-#pragma once
+#include <vector>
+
+#include "video_topk.h"
 
 namespace vfr {
 
@@ -328,7 +330,7 @@ struct ParWs {
 static ParWs carve_par(void *base, int64_t Nq, int64_t Ng, int Nv, int total_clips)
 {
     ParWs w{};
-    w.mw = carve_mfma(base, 1, 1, total_clips, 0);      // the front depends on total_clips alone (VFR_MFMA_BANK_READY, device hash)
+    w.mw = carve_bank_front(base, total_clips);
     size_t off = (size_t)(reinterpret_cast<char *>(w.mw.stale) - static_cast<char *>(base)) + 256;
     auto take = [&](size_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes, 256); return p; };
     w.qmeta = reinterpret_cast<float4 *>(take((size_t)Nq * 16));
@@ -418,8 +420,7 @@ int vfr_score_paragraphs_f32(const float *Q, int64_t Nq, const int64_t *grp_off,
     if (fast) {
         if (int rc = vfr::vtk_prepass(w.mw, w.qc, w.qmeta, Q, Nq, V, clip_offsets, Nv, total_clips, D, eps, bank_ready, st)) return rc;
         vfr::ProfScope prof(vfr::SITE_SCORE_FUSED, st);
-        hipLaunchKernelGGL(vfr::vtk_bounds_kernel, dim3((unsigned)vfr::cdiv(Nv, vfr::VTK_VIDEOS), (unsigned)vfr::cdiv(Nq, 64)), dim3(64), 0, st,
-                           w.qc, Nq, w.mw.vc, w.mw.va, w.qmeta, clip_offsets, Nv, total_clips, w.m2);
+        vfr::vtk_launch_bounds(w.qc, Nq, w.mw, w.qmeta, clip_offsets, Nv, total_clips, w.m2, st);
         hipLaunchKernelGGL(vfr::par_select_kernel, dim3((unsigned)Ng), dim3(256), 0, st, w.m2, Nq, grp_off, max_len, Nv, k, w.qmeta, own_dist,
                            count_lt, w.glo, w.ghi, w.list, w.list_len, w.n_undecided);
         VFR_CHECK_LAUNCH("vtk_bounds_kernel / par_select_kernel");
@@ -439,7 +440,7 @@ int vfr_score_paragraphs_f32(const float *Q, int64_t Nq, const int64_t *grp_off,
     }
     if (k > 0) {
         vfr::ProfScope prof(vfr::SITE_TOPK_MERGE, st);
-        hipLaunchKernelGGL(vfr::vtk_topk_kernel, dim3((unsigned)Ng), dim3(256), 0, st, w.keys, list_len, Nv, k, out_dist, out_idx);
+        vfr::vtk_launch_topk(w.keys, list_len, Ng, Nv, k, out_dist, out_idx, st);
         VFR_CHECK_LAUNCH("vtk_topk_kernel");
     }
     return VFR_OK;

@@ -12,179 +12,17 @@
 //     scored are wave-uniform, staged per wave into LDS with coalesced 16-byte loads and read back as broadcast ds_read_b128
 //     (no barrier, a wave never waits for another); branch-free moment triangle on register sums with thresholds as integer
 //     bounds on the fp32 bits of the SUM (no division, no key on the common path).  Details at the kernel.
-//   * score_mfma.h (included below): the MFMA pre-filter -- approximate distances from the GEMM form on the matrix cores,
+//   * score_mfma.h (included below the fast kernel): the MFMA pre-filter -- approximate distances from the GEMM form on the matrix cores,
 //     three-way threshold tests with a rigorous error margin, exact re-scoring of whatever the margin cannot decide.
 //   * keys are (fp32 bits of score << 32 | moment id): scores are >= 0 so unsigned order == the (score, id) lexicographic
 //     order, one 64-bit compare per test.
 #include <cstdlib>
-#include <type_traits>
 #include <vector>
 
-#include "vfr_common.h"
-#include "vfr_math.h"
+#include "score_device.h"
+#include "score_internal.h"
 
 namespace vfr {
-
-constexpr int NMAX_FUSED = 64;    // max clips per video on the fused path
-constexpr int NMAX_DENSE = 128;   // max clips per video on the dense / own paths
-constexpr unsigned long long KEY_MAX = ~0ull;
-constexpr unsigned long long KEY_EMPTY = 0x7F800000FFFFFFFFull;   // (+inf, max id): an unused slot of an exchanged list
-constexpr int MAX_RANK = 4;       // rank keys per query counted in one pass (IoU thresholds)
-
-// ------------------------------------------------------------------------------------------------
-// distance of NC (<= 4) clips to this lane's query: D is a template constant when DT > 0 (query in
-// registers), runtime when DT == 0 (query re-read from global, L1-resident).
-// ------------------------------------------------------------------------------------------------
-template <int DT, int NC>
-__device__ __forceinline__ void clip_dist4(const float *__restrict__ V, int64_t crow, int D, float eps,
-                                           const float *qreg, const float *__restrict__ qrow, float *out)
-{
-    float acc[NC];
-#pragma unroll
-    for (int i = 0; i < NC; ++i) acc[i] = 0.0f;
-    const float *v = V + crow * (DT > 0 ? DT : D);
-    if constexpr (DT > 0) {
-#pragma unroll
-        for (int k = 0; k < DT; ++k) {
-#pragma unroll
-            for (int i = 0; i < NC; ++i) {
-                float d = (v[i * DT + k] - qreg[k]) + eps;
-                acc[i] = __builtin_fmaf(d, d, acc[i]);
-            }
-        }
-    } else {
-        for (int k = 0; k < D; ++k) {
-            float qk = qrow[k];
-#pragma unroll
-            for (int i = 0; i < NC; ++i) {
-                float d = (v[(int64_t)i * D + k] - qk) + eps;
-                acc[i] = __builtin_fmaf(d, d, acc[i]);
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NC; ++i) out[i] = __builtin_sqrtf(acc[i]);
-}
-
-// all n clip distances of one video into the wave's LDS column ds[c*64 + lane]
-template <int DT>
-__device__ __forceinline__ void video_distances(const float *__restrict__ V, int c0, int n, int D, float eps,
-                                                const float *qreg, const float *__restrict__ qrow, float *ds,
-                                                int lane)
-{
-    int c = 0;
-    for (; c + 4 <= n; c += 4) {
-        float d[4];
-        clip_dist4<DT, 4>(V, c0 + c, D, eps, qreg, qrow, d);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ds[(c + i) * 64 + lane] = d[i];
-    }
-    for (; c < n; ++c) {
-        float d[1];
-        clip_dist4<DT, 1>(V, c0 + c, D, eps, qreg, qrow, d);
-        ds[c * 64 + lane] = d[0];
-    }
-}
-
-// value of lane (lane ^ STRIDE): within a row of 16 lanes through the DPP data path (one or two v_mov_b32_dpp per dword, a
-// few cycles), across rows through ds_bpermute (an LDS round trip).  26 of the 33 cross-lane stages of the 256-key sort
-// have STRIDE <= 8, and the stages depend on each other: the round trips were the sort's time.
-template <int STRIDE>
-__device__ __forceinline__ unsigned xor_lane_u32(unsigned x)
-{
-    if constexpr (STRIDE == 1) return (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, 0xB1, 0xF, 0xF, false);      // quad_perm [1,0,3,2]
-    else if constexpr (STRIDE == 2) return (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x4E, 0xF, 0xF, false); // quad_perm [2,3,0,1]
-    else if constexpr (STRIDE == 4) {
-        const int t = __builtin_amdgcn_update_dpp((int)x, (int)x, 0x104, 0xF, 0x5, false);       // row_shl:4 into banks 0, 2 (lane <- lane + 4)
-        return (unsigned)__builtin_amdgcn_update_dpp(t, (int)x, 0x114, 0xF, 0xA, false);          // row_shr:4 into banks 1, 3 (lane <- lane - 4)
-    } else if constexpr (STRIDE == 8) {
-        const int t = __builtin_amdgcn_update_dpp((int)x, (int)x, 0x108, 0xF, 0x3, false);       // row_shl:8 into banks 0, 1
-        return (unsigned)__builtin_amdgcn_update_dpp(t, (int)x, 0x118, 0xF, 0xC, false);          // row_shr:8 into banks 2, 3
-    } else return (unsigned)__shfl_xor((int)x, STRIDE, 64);
-}
-template <int STRIDE>
-__device__ __forceinline__ unsigned long long xor_lane_u64(unsigned long long x)
-{
-    return ((unsigned long long)xor_lane_u32<STRIDE>((unsigned)(x >> 32)) << 32) | xor_lane_u32<STRIDE>((unsigned)x);
-}
-
-// ------------------------------------------------------------------------------------------------
-// wave-cooperative bitonic sort of KPL*64 keys, element e = i*64 + lane, ascending
-// ------------------------------------------------------------------------------------------------
-template <int KPL>
-__device__ __forceinline__ void wave_sort(unsigned long long (&key)[KPL], int lane)
-{
-    constexpr int CAP = KPL * 64;
-#pragma unroll
-    for (int size = 2; size <= CAP; size <<= 1) {
-#pragma unroll
-        for (int stride = size >> 1; stride >= 1; stride >>= 1) {
-            if (stride >= 64) {
-                const int j = stride >> 6;
-#pragma unroll
-                for (int i = 0; i < KPL; ++i) {
-                    if ((i & j) == 0) {
-                        const bool asc = size >= CAP ? true : ((i & (size >> 6)) == 0);
-                        unsigned long long a = key[i], b = key[i | j];
-                        unsigned long long lo = a < b ? a : b, hi = a < b ? b : a;
-                        key[i] = asc ? lo : hi;
-                        key[i | j] = asc ? hi : lo;
-                    }
-                }
-            } else {
-                const bool lower = (lane & stride) == 0;
-#pragma unroll
-                for (int i = 0; i < KPL; ++i) {
-                    bool asc;
-                    if (size >= CAP) asc = true;
-                    else if (size >= 64) asc = (i & (size >> 6)) == 0;
-                    else asc = (lane & size) == 0;
-                    // the lane keeps its key when (it wants the smaller one) == (its key is the smaller one): one 64-bit
-                    // compare and two selects (min / max / select took ten vector instructions per key and stage)
-                    const unsigned long long other = stride == 1 ? xor_lane_u64<1>(key[i]) : stride == 2 ? xor_lane_u64<2>(key[i])
-                                                   : stride == 4 ? xor_lane_u64<4>(key[i]) : stride == 8 ? xor_lane_u64<8>(key[i])
-                                                   : stride == 16 ? xor_lane_u64<16>(key[i]) : xor_lane_u64<32>(key[i]);
-                    const bool keep = (lower == asc) == (key[i] < other);
-                    key[i] = keep ? key[i] : other;
-                }
-            }
-        }
-    }
-}
-
-template <int KPL>
-__device__ __forceinline__ unsigned long long key_at(const unsigned long long (&key)[KPL], int e)
-{
-    unsigned long long r = 0;
-    const int i = e >> 6, l = e & 63;
-#pragma unroll
-    for (int j = 0; j < KPL; ++j)
-        if (j == i) r = __shfl(key[j], l, 64);
-    return r;
-}
-
-// compact the candidate buffer of lane L (wave-uniform): keep the k smallest keys, sorted.
-// returns the new count; *thr_out = k-th smallest key when at least k keys exist.
-template <int KPL>
-__device__ __attribute__((noinline)) int compact_buffer(unsigned long long *base, int cnt, int k, int lane,
-                                              unsigned long long *thr_out)
-{
-    unsigned long long key[KPL];
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        int e = i * 64 + lane;
-        key[i] = e < cnt ? base[e] : KEY_MAX;
-    }
-    wave_sort<KPL>(key, lane);
-    const int keep = cnt < k ? cnt : k;
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        int e = i * 64 + lane;
-        if (e < keep) base[e] = key[i];
-    }
-    if (cnt >= k) *thr_out = key_at<KPL>(key, k - 1);
-    return keep;
-}
 
 struct MfmaArgs;
 
@@ -369,7 +207,6 @@ __global__ __launch_bounds__(256) void score_kernel(const float *__restrict__ Qp
 //     64-bit keys, buffer appends) -- rare once the shared threshold has tightened.
 // ================================================================================================
 typedef float float2v __attribute__((ext_vector_type(2)));
-constexpr int FAST_D = 100;
 
 __device__ __forceinline__ float next_up(float x) { return __uint_as_float(__float_as_uint(x) + 1u); }
 __device__ __forceinline__ float next_down(float x) { return __uint_as_float(__float_as_uint(x) - 1u); }
@@ -966,186 +803,6 @@ __global__ __launch_bounds__(256) void topk_kth_seed_kernel(const unsigned long 
     }
 }
 
-// merge G shard lists [G, Nq, k] -> [Nq, k] (after the all-gather, 8e).  Lists arrive either as (dist, idx) arrays or as
-// the packed int64 keys the ranks exchange (KEY_EMPTY = (+inf, 0xffffffff) marks an unused slot).  Same LDS pool as the
-// task merge: all G*k keys are read as one flat sequence, CAP per round with the loads in flight together, and a key is
-// appended only if it beats the running k-th key -- after the first round almost nothing is, so a query costs ~2 sorts.
-template <int KPL, bool PACKED>
-__global__ __launch_bounds__(256) void topk_merge_parts_kernel(const float *__restrict__ pd,
-                                                               const int64_t *__restrict__ pi, int64_t slot_stride,
-                                                               int64_t q_stride, int G, int64_t Nq, int k,
-                                                               float *__restrict__ out_dist,
-                                                               int64_t *__restrict__ out_idx,
-                                                               int64_t *__restrict__ out_keys)
-{
-    constexpr int CAP = KPL * 64;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t q = (int64_t)blockIdx.x * 4 + wv;
-    if (q >= Nq) return;
-    __shared__ unsigned long long pool_s[4][CAP];
-    unsigned long long *pool = pool_s[wv];
-    unsigned long long key[KPL];
-    unsigned long long thr = KEY_MAX;
-    int fill = 0;
-    auto lds_sync = [&]() { __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_wave_barrier(); };
-    auto sort_pool = [&](bool final_pass) {
-        lds_sync();
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) { const int e = i * 64 + lane; key[i] = e < fill ? pool[e] : KEY_MAX; }
-        wave_sort<KPL>(key, lane);
-        if (final_pass) return;
-        lds_sync();
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) { const int e = i * 64 + lane; if (e < k) pool[e] = key[i]; }
-        if (fill >= k) thr = key_at<KPL>(key, k - 1);
-        fill = fill < k ? fill : k;
-    };
-    const int total = G * k;
-    for (int done = 0; done < total; done += CAP) {
-        unsigned long long x[KPL];
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) {
-            const int gi = done + i * 64 + lane;
-            x[i] = KEY_MAX;
-            if (gi < total) {
-                const int g = gi / k, off = gi - g * k;
-                const int64_t at = (int64_t)g * slot_stride + q * q_stride + off;  // [G, Nq, k]: slot_stride = Nq * k, q_stride = k
-                if constexpr (PACKED) {
-                    const unsigned long long v = (unsigned long long)pi[at];
-                    x[i] = v >= KEY_EMPTY ? KEY_MAX : v;
-                } else {
-                    const int64_t id = pi[at];
-                    x[i] = id < 0 ? KEY_MAX : make_key(pd[at], (unsigned)id);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) {
-            if (fill + 64 > CAP) sort_pool(false);
-            const bool pass = x[i] < thr;                        // KEY_MAX (empty) never passes
-            const unsigned long long m = __ballot(pass);
-            if (pass) pool[fill + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = x[i];
-            fill += __builtin_popcountll(m);
-        }
-    }
-    sort_pool(true);
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        int e = i * 64 + lane;
-        if (e < k) {
-            const bool ok = key[i] != KEY_MAX;
-            if (out_dist) {
-                out_dist[q * k + e] = ok ? __uint_as_float((unsigned)(key[i] >> 32)) : __builtin_inff();
-                out_idx[q * k + e] = ok ? (int64_t)(key[i] & 0xffffffffull) : -1;
-            }
-            if (out_keys) out_keys[q * k + e] = (int64_t)(ok ? key[i] : KEY_EMPTY);
-        }
-    }
-}
-
-// (dist, idx) lists -> the packed int64 keys the ranks exchange (one collective instead of two); idx < 0 -> KEY_EMPTY
-__global__ __launch_bounds__(256) void topk_pack_keys_kernel(const float *__restrict__ d, const int64_t *__restrict__ ix,
-                                                             int64_t n, int64_t *__restrict__ keys)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int64_t id = ix[i];
-    keys[i] = (int64_t)(id < 0 ? KEY_EMPTY : make_key(d[i], (unsigned)id));
-}
-
-// best ground-truth-positive key per (threshold, query):  min over the labelled moments of the query's own video of
-// (score, global id)  (evaluate.py:67-77: the first positive in the sorted order).  One wave per selected query.
-__global__ __launch_bounds__(256) void gt_fill_keys_kernel(int64_t n, int64_t *__restrict__ keys)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) keys[i] = (int64_t)KEY_EMPTY;
-}
-// the same initialisation with the unpacked forms of vfr_gt_rank_keys_f32: distance +inf, id 0xffffffff, counts 0, flag 0
-__global__ __launch_bounds__(256) void gt_fill_rank_kernel(int64_t n, int64_t *__restrict__ keys, float *__restrict__ rank_dist,
-                                                           int64_t *__restrict__ rank_idx, int64_t *__restrict__ count0,
-                                                           int *__restrict__ missing)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i == 0 && missing) *missing = 0;
-    if (i >= n) return;
-    keys[i] = (int64_t)KEY_EMPTY;
-    if (rank_dist) { rank_dist[i] = __builtin_inff(); rank_idx[i] = 0xFFFFFFFFll; }
-    if (count0) count0[i] = 0;
-}
-__global__ __launch_bounds__(256) void gt_best_keys_kernel(const float *__restrict__ sc, int64_t n_sel, int M,
-                                                           int score_stride, const uint8_t *__restrict__ labels, int R,
-                                                           int label_stride, const int64_t *__restrict__ id_base,
-                                                           const int64_t *__restrict__ sel, int64_t Nq,
-                                                           int64_t *__restrict__ keys, float *__restrict__ rank_dist = nullptr,
-                                                           int64_t *__restrict__ rank_idx = nullptr, int *__restrict__ missing = nullptr)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (s >= n_sel) return;
-    const int64_t base = id_base[s], q = sel[s];
-    for (int r = 0; r < R; ++r) {
-        unsigned long long best = KEY_MAX;
-        const uint8_t *lab = labels + ((int64_t)r * n_sel + s) * label_stride;
-        for (int m = lane; m < M; m += 64)
-            if (lab[m]) {
-                const unsigned long long kk = make_key(sc[s * score_stride + m], (unsigned)(base + m));
-                best = kk < best ? kk : best;
-            }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const unsigned long long o = __shfl_xor(best, d, 64);
-            best = o < best ? o : best;
-        }
-        if (lane == 0) {
-            const unsigned long long kq = best >= KEY_EMPTY ? KEY_EMPTY : best;
-            keys[(int64_t)r * Nq + q] = (int64_t)kq;
-            if (rank_dist) {
-                rank_dist[(int64_t)r * Nq + q] = __uint_as_float((unsigned)(kq >> 32));
-                rank_idx[(int64_t)r * Nq + q] = (int64_t)(kq & 0xffffffffull);
-            }
-            if (missing && kq == KEY_EMPTY) atomicOr(missing, 1);
-        }
-    }
-}
-
-// a11 (model/evaluate.py:59-62, utils.get_iou model/utils.py:78-82): labels[r][q][m] = 1 iff at least two annotators have
-// IoU > (or >=) thr[r] with local moment m of the query's own video.  One thread per (query, moment); the IoU is the
-// reference's float64 intersection / union (IEEE division: the same bits as numpy's).
-constexpr int MAX_LABEL_THR = 16;
-struct LabelThr { double t[MAX_LABEL_THR]; };
-__global__ __launch_bounds__(256) void gt_labels_kernel(const int32_t *__restrict__ times, const int32_t *__restrict__ nannot,
-                                                        const int32_t *__restrict__ n_own, int64_t Nq, int A, int R,
-                                                        LabelThr thr, int strict, int Mmax, uint8_t *__restrict__ labels)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= Nq * Mmax) return;
-    const int64_t q = i / Mmax;
-    const int m = (int)(i - q * Mmax), n = n_own[q];
-    int s = m, e = m;                                     // generate_moments order: (j, j) first, then combinations
-    bool real = m < n * (n + 1) / 2;
-    if (real && m >= n) {
-        int rest = m - n;
-        s = 0;
-        while (rest >= n - 1 - s) { rest -= n - 1 - s; ++s; }
-        e = s + 1 + rest;
-    }
-    int cnt[MAX_LABEL_THR];
-#pragma unroll
-    for (int r = 0; r < MAX_LABEL_THR; ++r) cnt[r] = 0;
-    const int na = nannot[q];
-    for (int a = 0; a < na && real; ++a) {
-        const int ts = times[(q * A + a) * 2], te = times[(q * A + a) * 2 + 1];
-        const int inter = max(min(te, e) + 1 - max(ts, s), 0), uni = max(te, e) + 1 - min(ts, s);
-        const double iou = (double)inter / (double)uni;
-#pragma unroll
-        for (int r = 0; r < MAX_LABEL_THR; ++r)
-            if (r < R) cnt[r] += (strict ? iou > thr.t[r] : iou >= thr.t[r]) ? 1 : 0;
-    }
-#pragma unroll
-    for (int r = 0; r < MAX_LABEL_THR; ++r)
-        if (r < R) labels[((int64_t)r * Nq + q) * Mmax + m] = cnt[r] >= 2 ? 1 : 0;
-}
-
 // each query against its own video (evaluate_single.py:48-53).  One WAVE per query: lane c runs clip c's k-ascending
 // distance chain (the clips of a video are independent chains), the distances go through LDS, then lane s walks the spans
 // (s, s), (s, s+1), ... keeping the left-to-right running sum of the oracle.  (Thread-per-query left the chip to 79 waves
@@ -1213,7 +870,6 @@ static void plan_tasks(int64_t Nq, int Nv, int *groups, int *chunks)
     *groups = g;
     *chunks = c;
 }
-static int kpl_for(int k) { return k <= 128 ? 4 : 8; }
 
 // Threshold ladder of the top-k pass (k > 0, fast path).  The fused kernel appends every moment that beats the query's
 // current threshold, so the threshold's quality decides how often its exact path runs:
@@ -1449,6 +1105,18 @@ static int run_pass(ScoreArgs a, const TopkWs &w, bool seeded, float *out_dist, 
     return VFR_OK;
 }
 
+// what every fused pass takes over from its entry point's arguments; everything else starts as zero
+static ScoreArgs pass_args(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv,
+                           int total_clips, int min_clips, int max_clips, int D, float eps, int64_t id_base, int k, int num_rank,
+                           const float *rank_dist, const int64_t *rank_idx, int64_t *count_lt)
+{
+    ScoreArgs a{};
+    a.Q = Q; a.Nq = Nq; a.V = V; a.clip_off = clip_offsets; a.mom_off = moment_offsets; a.Nv = Nv; a.D = D; a.eps = eps;
+    a.id_base = id_base; a.k = k; a.num_rank = num_rank; a.rank_dist = rank_dist; a.rank_idx = rank_idx; a.count_lt = count_lt;
+    a.ds_rows = max_clips < 1 ? 1 : max_clips; a.total_clips = total_clips; a.min_clips = min_clips;
+    return a;
+}
+
 }  // namespace vfr
 
 extern "C" {
@@ -1515,12 +1183,8 @@ int vfr_score_topk_f32(const float *Q, int64_t Nq, const float *V, const int32_t
                 "vfr_score_topk_f32: workspace %zu < %zu bytes", workspace_bytes,
                 vfr_score_topk_workspace_bytes(Nq, Nv, k));
     vfr::TopkWs w = vfr::carve_topk(workspace, Nq, Nv, k);
-    vfr::ScoreArgs a{};
-    a.Q = Q; a.Nq = Nq; a.V = V; a.clip_off = clip_offsets; a.mom_off = moment_offsets; a.Nv = Nv; a.D = D; a.eps = eps;
-    a.id_base = id_base; a.k = k; a.num_rank = num_rank; a.rank_dist = rank_dist; a.rank_idx = rank_idx; a.count_lt = count_lt;
-    a.ds_rows = max_clips < 1 ? 1 : max_clips;
-    a.total_clips = total_clips;
-    a.min_clips = min_clips;
+    vfr::ScoreArgs a = vfr::pass_args(Q, Nq, V, clip_offsets, moment_offsets, Nv, total_clips, min_clips, max_clips, D, eps, id_base, k,
+                                      num_rank, rank_dist, rank_idx, count_lt);
     if (Nv > 0 && k > 0) {
         if (int rc = thr_seed ? vfr::copy_region(w.thr, thr_seed, (size_t)Nq * 8, st) : vfr::fill_region(w.thr, 0xFFFFFFFFu, (size_t)Nq * 8, st)) return rc;
     }
@@ -1532,15 +1196,7 @@ int vfr_score_topk_f32(const float *Q, int64_t Nq, const float *V, const int32_t
 
 // ---- MFMA pre-filter path (score_mfma.h) ------------------------------------------------------------------------------
 namespace vfr {
-struct MfmaWs {
-    float *rv; BankSig *sig; unsigned long long *hash_now; int *stale; int *fallback; unsigned long long *pairs_total; unsigned long long *cnt_ws; size_t zero_bytes; char *zero_base;
-    float *va; float4 *qmeta; unsigned *tab; unsigned *wmax, *qbound; unsigned short *vb; ulonglong2 *amb; int tasks, groups;
-    float *mu, *vc, *qc; double *mean_partial; int mean_blocks, mean_rows;
-    signed char *vl, *ql; float2 *mean_minmax; double *bankc; float *qf; double2 *qdbg; double *qscale;   // int8 operand mode
-    void *topk; size_t topk_bytes; size_t total;
-    int *perm, *diff; unsigned *hist; uint2 *hrange; float *Qs, *rds; int64_t *ris, *seeds, *cnts; float *ods; int64_t *ois;
-};
-static MfmaWs carve_mfma(void *base, int64_t Nq, int Nv, int total_clips, int k)
+MfmaWs carve_mfma(void *base, int64_t Nq, int Nv, int total_clips, int k)
 {
     MfmaWs w{};
     int g, c;
@@ -1618,481 +1274,53 @@ __global__ __launch_bounds__(256) void mfma_seed_kernel(const int64_t *__restric
     }
     thr[q] = t;
 }
-// ---- a handful of queries (one serving request) ---------------------------------------------------------------------
-constexpr int SMALLQ_CLIPS_MAX = 21;
-// The fused kernels put QUERIES on the lanes: with 1-8 queries a wave is 2-12 % full and the pass costs 0.55 ms however
-// little there is to score.  Here the lanes are clips and videos: every clip distance once (lane = clip, the canonical chain
-// against all NQ queries while the row streams past), then lane = video writes the keys of its moments -- the canonical sums
-// and IEEE quotients of the dense kernel -- and counts them against the rank keys; the top-k is two rounds of the pool
-// selection of topk_merge_parts_kernel over the key array (P ranges per query, then the P lists).  Exact like every f32 path.
-template <int NQ>
-__global__ __launch_bounds__(256) void smallq_dist_kernel(const float *__restrict__ Q, int Nq, const float *__restrict__ V,
-                                                          int total_clips, int D, float eps, float *__restrict__ dist)
+MfmaWs carve_bank_front(void *base, int total_clips)
 {
-    // D = 100 (the model's embedding width; other widths take the general loop below): the lane's whole row is requested at
-    // once (25 loads in flight), the queries sit in LDS and are read as broadcasts
-    __shared__ __attribute__((aligned(16))) float qs[NQ][FAST_D];
-    // blockIdx.y = group of NQ queries: all groups of a request in ONE launch (eight launches of 27 us each were 12 us of
-    // arithmetic and 15 of launch gap, ramp and a 3.2-blocks-per-CU round each)
-    Q += (int64_t)blockIdx.y * NQ * D;
-    dist += (int64_t)blockIdx.y * NQ * total_clips;
-    Nq = Nq - (int)blockIdx.y * NQ < NQ ? Nq - (int)blockIdx.y * NQ : NQ;
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    float acc[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) acc[q] = 0.0f;
-    if (D == FAST_D) {
-        for (int i = threadIdx.x; i < NQ * FAST_D; i += 256) qs[i / FAST_D][i % FAST_D] = Q[(int64_t)(i / FAST_D < Nq ? i / FAST_D : 0) * FAST_D + i % FAST_D];
-        float4 row[FAST_D / 4];
-        const float4 *v4 = reinterpret_cast<const float4 *>(V + (int64_t)(c < total_clips ? c : total_clips - 1) * FAST_D);
-#pragma unroll
-        for (int k4 = 0; k4 < FAST_D / 4; ++k4) row[k4] = v4[k4];
-        __syncthreads();
-#pragma unroll
-        for (int k4 = 0; k4 < FAST_D / 4; ++k4) {
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const float4 qq = *reinterpret_cast<const float4 *>(&qs[q][4 * k4]);
-                float t = (row[k4].x - qq.x) + eps; acc[q] = __builtin_fmaf(t, t, acc[q]);
-                t = (row[k4].y - qq.y) + eps; acc[q] = __builtin_fmaf(t, t, acc[q]);
-                t = (row[k4].z - qq.z) + eps; acc[q] = __builtin_fmaf(t, t, acc[q]);
-                t = (row[k4].w - qq.w) + eps; acc[q] = __builtin_fmaf(t, t, acc[q]);
-            }
-        }
-    } else if (c < total_clips) {
-        const float *v = V + (int64_t)c * D;
-        for (int k = 0; k < D; ++k) {
-            const float vk = v[k];
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const float t = (vk - Q[(int64_t)(q < Nq ? q : 0) * D + k]) + eps;
-                acc[q] = __builtin_fmaf(t, t, acc[q]);
-            }
-        }
-    }
-    if (c >= total_clips) return;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-        if (q < Nq) dist[(int64_t)q * total_clips + c] = __builtin_sqrtf(acc[q]);
-}
-
-// 16 videos per block, 16 threads per video (thread = the moments starting at clip s, s + 16, ...): canonical sums and
-// quotients, keys staged in LDS at their moment index and written out as one contiguous run (the videos' moments are
-// adjacent), rank counts reduced over the block
-constexpr int SQ_VIDEOS = 16, SQ_MOM = SMALLQ_CLIPS_MAX * (SMALLQ_CLIPS_MAX + 1) / 2;
-__global__ __launch_bounds__(256) void smallq_moments_kernel(const float *__restrict__ dist, int Nq, const int32_t *__restrict__ clip_off,
-                                                             const int64_t *__restrict__ mom_off, int Nv, int total_clips, int64_t id_base,
-                                                             unsigned long long *__restrict__ keys, int64_t Mpad, int num_rank,
-                                                             const float *__restrict__ rank_dist, const int64_t *__restrict__ rank_idx,
-                                                             int64_t *__restrict__ count_lt, float *__restrict__ dmin)
-{
-    __shared__ unsigned long long stage[SQ_VIDEOS * SQ_MOM];
-    __shared__ float ds[SQ_VIDEOS][SMALLQ_CLIPS_MAX + 3];
-    __shared__ int red[MAX_RANK][4];
-    const int q = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int vl = threadIdx.x >> 4, sl = threadIdx.x & 15;                   // video within the block, first start clip
-    const int v0 = blockIdx.x * SQ_VIDEOS, v = v0 + vl;
-    unsigned long long kstar[MAX_RANK] = {0, 0, 0, 0};
-    for (int r = 0; r < num_rank; ++r) kstar[r] = make_key(rank_dist[(int64_t)r * Nq + q], (unsigned)rank_idx[(int64_t)r * Nq + q]);
-    int nlt[MAX_RANK] = {0, 0, 0, 0};
-    const int vhi = v0 + SQ_VIDEOS < Nv ? v0 + SQ_VIDEOS : Nv;
-    const int64_t mb0 = mom_off[v0], mb1 = mom_off[vhi];                      // the block's run of moments
-    int n = 0, c0 = 0;
-    int64_t m0 = 0;
-    if (v < Nv) { c0 = clip_off[v]; n = clip_off[v + 1] - c0; m0 = mom_off[v]; }
-    float dm = __builtin_inff();
-    for (int c = sl; c < n; c += 16) { const float dv = dist[(int64_t)q * total_clips + c0 + c]; ds[vl][c] = dv; dm = dv < dm ? dv : dm; }
-    if (dmin) {           // the video's smallest clip distance = the score of its best one-clip moment (top-k selection below)
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { const float t = __shfl_xor(dm, o, 64); dm = t < dm ? t : dm; }
-        if (sl == 0 && v < Nv) dmin[(int64_t)q * Nv + v] = dm;
-    }
-    __syncthreads();
-    for (int s = sl; s < n; s += 16) {
-        float sum = 0.0f;
-        for (int e = s; e < n; ++e) {
-            const float de = ds[vl][e];
-            sum = e == s ? de : sum + de;
-            const float sc = sum / (float)(e - s + 1);
-            const int64_t m = m0 + moment_index(n, s, e);
-            const unsigned long long key = make_key(sc, (unsigned)(id_base + m));
-            stage[m - mb0] = key;
-#pragma unroll
-            for (int r = 0; r < MAX_RANK; ++r) nlt[r] += key < kstar[r] ? 1 : 0;     // kstar = 0 when unused
-        }
-    }
-    for (int r = 0; r < num_rank; ++r) {
-        int x = nlt[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        if (lane == 0) red[r][wv] = x;
-    }
-    __syncthreads();
-    if (keys)
-        for (int64_t i = threadIdx.x; i < mb1 - mb0; i += 256) keys[(int64_t)q * Mpad + mb0 + i] = stage[i];
-    if ((int)threadIdx.x < num_rank) {
-        const int r = threadIdx.x;
-        const long long t = (long long)red[r][0] + red[r][1] + red[r][2] + red[r][3];
-        if (t) atomicAdd(reinterpret_cast<unsigned long long *>(count_lt + (int64_t)r * Nq + q), (unsigned long long)t);
-    }
-}
-
-// Rank counts + per-video smallest clip distance for the video-selection form (no key array wanted): lane = VIDEO.  The moment
-// kernel above gives a video to 16 threads by start clip -- thread 0 of a 21-clip video walks 26 moments, thread 15 six, and every
-// moment pays an LDS key store, four 64-bit compares, a run-time moment index and an 11-instruction IEEE division: 0.32 ms at 64
-// queries x 10 000 videos, a quarter of that request.  Here a lane keeps its video's distances in registers (+inf past its clip
-// count: such moments compare false), the triangle is straight-line code -- the canonical sum (clips left to right from the start
-// clip), the quotient by a compile-time length as c_div_small (3 instructions, the IEEE quotient for every sum in [2^-60, 2^100]:
-// vfr_math.h), two float compares per rank key -- and the moment id only exists on the slow path: a lane whose score EQUALS a rank
-// distance somewhere (the id decides), or whose distances leave that range, redoes its video with keys and IEEE divisions.
-// One wave per 64 videos and query; from `score_smallq_rank` (8) queries on -- below, the 16-threads-per-video form has more waves
-// in flight for the same work and finishes sooner.
-template <int NT, int NR>
-__global__ __launch_bounds__(64) void smallq_rank_kernel(const float *__restrict__ dist, int Nq, const int32_t *__restrict__ clip_off,
-                                                         const int64_t *__restrict__ mom_off, int Nv, int total_clips, int64_t id_base,
-                                                         int num_rank, const float *__restrict__ rank_dist, const int64_t *__restrict__ rank_idx,
-                                                         int64_t *__restrict__ count_lt, float *__restrict__ dmin)
-{
-    const int q = blockIdx.y, lane = threadIdx.x;
-    const int v = blockIdx.x * 64 + lane;
-    int n = 0, c0 = 0;
-    if (v < Nv) { c0 = clip_off[v]; n = clip_off[v + 1] - c0; }
-    float d[NT];
-    float dm = __builtin_inff(), dx = 0.0f;
-#pragma unroll
-    for (int c = 0; c < NT; ++c) {
-        const float x = c < n ? dist[(int64_t)q * total_clips + c0 + c] : 0.0f;
-        dm = c < n && x < dm ? x : dm;
-        dx = x > dx ? x : dx;
-        d[c] = c < n ? x : __builtin_inff();
-    }
-    if (dmin && v < Nv) dmin[(int64_t)q * Nv + v] = dm;
-    if (num_rank == 0) return;
-    float kd[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) kd[r] = r < num_rank ? rank_dist[(int64_t)r * Nq + q] : -1.0f;     // (scores are >= 0: an unused key counts nothing)
-    int nlt[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) nlt[r] = 0;
-    // every sum of this video lies in [smallest distance, NT x largest]: inside c_div_small's range?
-    bool slow = n > 0 && (dm < C_DIV_SMALL_LO || dx > C_DIV_SMALL_HI / 32.0f);
-#pragma unroll
-    for (int s = 0; s < NT; ++s) {
-        float sum = d[s];
-#pragma unroll
-        for (int e = s; e < NT; ++e) {
-            if (e > s) sum = sum + d[e];
-            const float sc = c_div_small(sum, e - s + 1);
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                nlt[r] += sc < kd[r] ? 1 : 0;
-                slow = slow || sc == kd[r];
-            }
-        }
-    }
-    if (slow) {
-        unsigned long long kstar[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) { nlt[r] = 0; kstar[r] = r < num_rank ? make_key(kd[r], (unsigned)rank_idx[(int64_t)r * Nq + q]) : 0ull; }
-        const int64_t m0 = mom_off[v < Nv ? v : 0];
-        for (int s = 0; s < n; ++s) {
-            float sum = 0.0f;
-            for (int e = s; e < n; ++e) {
-                const float de = dist[(int64_t)q * total_clips + c0 + e];
-                sum = e == s ? de : sum + de;
-                const unsigned long long key = make_key(sum / (float)(e - s + 1), (unsigned)(id_base + m0 + moment_index(n, s, e)));
-#pragma unroll
-                for (int r = 0; r < NR; ++r) nlt[r] += key < kstar[r] ? 1 : 0;
-            }
-        }
-    }
-    for (int r = 0; r < NR; ++r) {
-        if (r >= num_rank) break;
-        int x = nlt[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        if (lane == 0 && x) atomicAdd(reinterpret_cast<unsigned long long *>(count_lt + (int64_t)r * Nq + q), (unsigned long long)x);
-    }
-}
-
-// One level of the selection tree over key lists [q][Pin][k]: wave (q, r) reads lists r*F .. r*F + F - 1 of query q as one
-// flat range -- the next round's keys requested before the current round is filtered -- keeps the k smallest in the LDS
-// pool of the merge kernels and writes them as list r of [q][Pout][k] (or, at the root, as the query's (dist, idx) rows).
-template <int KPL>
-__global__ __launch_bounds__(256) void topk_tree_kernel(const unsigned long long *__restrict__ in, int64_t Pin, int F, int64_t Pout,
-                                                        int64_t n_vq, int k, unsigned long long *__restrict__ out_keys,
-                                                        float *__restrict__ out_dist, int64_t *__restrict__ out_idx)
-{
-    constexpr int CAP = KPL * 64;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t vq = (int64_t)blockIdx.x * 4 + wv;
-    if (vq >= n_vq) return;
-    __shared__ unsigned long long pool_s[4][CAP];
-    unsigned long long *pool = pool_s[wv];
-    unsigned long long key[KPL];
-    unsigned long long thr = KEY_MAX;
-    int fill = 0;
-    auto lds_sync = [&]() { __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_wave_barrier(); };
-    auto sort_pool = [&](bool final_pass) {
-        lds_sync();
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) { const int e = i * 64 + lane; key[i] = e < fill ? pool[e] : KEY_MAX; }
-        wave_sort<KPL>(key, lane);
-        if (final_pass) return;
-        lds_sync();
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) { const int e = i * 64 + lane; if (e < k) pool[e] = key[i]; }
-        if (fill >= k) thr = key_at<KPL>(key, k - 1);
-        fill = fill < k ? fill : k;
-    };
-    const int64_t q = vq / Pout, r = vq - q * Pout, first = r * F;
-    const int64_t nl = Pin - first < F ? Pin - first : F;
-    const unsigned long long *src = in + (q * Pin + first) * k;
-    const int64_t total = nl * k;
-    // NB rounds of CAP keys are requested together and the next NB before these are filtered: a wave is alone with its
-    // range, so the memory latency it pays is per batch of requests, not per round
-    constexpr int NB = 4;
-    unsigned long long x[NB][KPL], xn[NB][KPL];
-    auto load = [&](unsigned long long (&dst)[NB][KPL], int64_t done) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int i = 0; i < KPL; ++i) {
-                const int64_t gi = done + (b * KPL + i) * 64 + lane;
-                const unsigned long long vv = src[gi < total ? gi : total - 1];
-                dst[b][i] = (gi < total && vv < KEY_EMPTY) ? vv : KEY_MAX;
-            }
-    };
-    load(x, 0);
-    for (int64_t done = 0; done < total; done += NB * CAP) {
-        load(xn, done + NB * CAP);
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int i = 0; i < KPL; ++i) {
-                if (fill + 64 > CAP) sort_pool(false);
-                const bool pass = x[b][i] < thr;                 // KEY_MAX (empty) never passes
-                const unsigned long long m = __ballot(pass);
-                if (pass) pool[fill + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = x[b][i];
-                fill += __builtin_popcountll(m);
-            }
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int i = 0; i < KPL; ++i) x[b][i] = xn[b][i];
-    }
-    sort_pool(true);
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        const int e = i * 64 + lane;
-        if (e < k) {
-            const bool ok = key[i] != KEY_MAX;
-            if (out_dist) {
-                out_dist[vq * k + e] = ok ? __uint_as_float((unsigned)(key[i] >> 32)) : __builtin_inff();
-                out_idx[vq * k + e] = ok ? (int64_t)(key[i] & 0xffffffffull) : -1;
-            } else {
-                out_keys[vq * k + e] = ok ? key[i] : KEY_EMPTY;
-            }
-        }
-    }
-}
-
-// Top-k of a handful of queries WITHOUT the key array and the selection tree (three latency-bound levels: 0.09 ms at one
-// query).  Every moment's score is a mean of its video's clip distances, so score >= dmin_v * (1 - 22 u) (dmin_v = the
-// video's smallest clip distance; each rounding is monotone), and dmin_v itself is the score of a one-clip moment.  Hence any
-// thr that is >= the k-th smallest dmin over the videos bounds the k-th best moment, and only videos with
-// dmin_v <= thr * (1 + 32 u) can hold a moment of the top-k.  One 1024-thread workgroup per query:
-//   A  thr: min / max of the dmin row, a 2048-bin histogram over [min, max], the first bin b* at which the running count
-//      reaches k; thr = the largest dmin in bins <= b* (>= k videos lie at or below it).  Nv <= k: thr = +inf (everything);
-//   B  the videos passing the margin test are listed in LDS (4096 at a time);
-//   C  thread = (listed video, start clip): the canonical sums and IEEE quotients of smallq_moments_kernel, keys <= (thr, max id)
-//      appended to the query's candidate run in global memory (the slot from an LDS counter: one workgroup owns the query);
-//   D  wave 0 runs the pool selection of the merge kernels over the candidates (typically a few hundred) and writes the rows.
-// Exact: the candidates are a superset of the top-k with the dense kernel's keys.
-constexpr int SQS_BINS = 2048, SQS_LIST = 4096, SQS_THREADS = 1024;
-static_assert(SQS_BINS == 2 * SQS_THREADS, "the bin scan gives every thread two bins");
-static_assert(SQS_LIST >= 2 * SQS_THREADS, "the video list must take at least one full chunk of candidates after a partial one");
-template <int KPL>
-__global__ __launch_bounds__(SQS_THREADS) void smallq_select_kernel(const float *__restrict__ dist, const float *__restrict__ dmin,
-                                                                    const int32_t *__restrict__ clip_off, const int64_t *__restrict__ mom_off,
-                                                                    int Nv, int total_clips, int64_t id_base, int k,
-                                                                    unsigned long long *__restrict__ cand, int64_t cand_stride,
-                                                                    float *__restrict__ out_dist, int64_t *__restrict__ out_idx)
-{
-    constexpr int CAP = KPL * 64;
-    __shared__ int hist[SQS_BINS];
-    __shared__ int vlist[SQS_LIST];
-    __shared__ float redf[2][SQS_THREADS / 64];
-    __shared__ int redi[SQS_THREADS / 64];
-    __shared__ int s_bstar, s_nlist, s_ncand;
-    __shared__ unsigned long long pool[CAP];
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float *dq = dmin + (int64_t)q * Nv;
-    unsigned long long *cq = cand + (int64_t)q * cand_stride;
-    // ---- A: threshold ----
-    float mn = __builtin_inff(), mx = 0.0f;
-    for (int v = tid; v < Nv; v += SQS_THREADS) { const float x = dq[v]; mn = x < mn ? x : mn; mx = (x > mx && x < __builtin_inff()) ? x : mx; }   // (a video without clips: +inf)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float a = __shfl_xor(mn, o, 64), b = __shfl_xor(mx, o, 64); mn = a < mn ? a : mn; mx = b > mx ? b : mx; }
-    if (lane == 0) { redf[0][wv] = mn; redf[1][wv] = mx; }
-    for (int i = tid; i < SQS_BINS; i += SQS_THREADS) hist[i] = 0;
-    if (tid == 0) { s_nlist = 0; s_ncand = 0; s_bstar = SQS_BINS - 1; }
-    __syncthreads();
-    mn = redf[0][0]; mx = redf[1][0];
-#pragma unroll
-    for (int i = 1; i < SQS_THREADS / 64; ++i) { mn = redf[0][i] < mn ? redf[0][i] : mn; mx = redf[1][i] > mx ? redf[1][i] : mx; }
-    const float scale = mx > mn ? (float)(SQS_BINS - 1) / (mx - mn) : 0.0f;
-    auto bin_of = [&](float x) {
-        if (!(x < __builtin_inff())) return SQS_BINS - 1;
-        const int b = (int)((x - mn) * scale);
-        return b < 0 ? 0 : (b > SQS_BINS - 1 ? SQS_BINS - 1 : b);
-    };
-    float thr = __builtin_inff();
-    if (Nv > k) {
-        for (int v = tid; v < Nv; v += SQS_THREADS) atomicAdd(&hist[bin_of(dq[v])], 1);
-        __syncthreads();
-        // running count over the bins: thread t owns bins 2t, 2t + 1
-        const int h0 = hist[2 * tid], h1 = hist[2 * tid + 1];
-        int part = h0 + h1, incl = part;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-        if (lane == 63) redi[wv] = incl;
-        __syncthreads();
-        int before = 0;
-        for (int i = 0; i < wv; ++i) before += redi[i];
-        const int excl = before + incl - part;                              // videos in bins < 2t
-        if (excl < k && excl + h0 >= k) s_bstar = 2 * tid;
-        else if (excl + h0 < k && excl + part >= k) s_bstar = 2 * tid + 1;
-        __syncthreads();
-        const int bstar = s_bstar;
-        float tm = 0.0f;
-        for (int v = tid; v < Nv; v += SQS_THREADS) { const float x = dq[v]; if (bin_of(x) <= bstar) tm = x > tm ? x : tm; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const float a = __shfl_xor(tm, o, 64); tm = a > tm ? a : tm; }
-        if (lane == 0) redf[0][wv] = tm;
-        __syncthreads();
-        tm = redf[0][0];
-#pragma unroll
-        for (int i = 1; i < SQS_THREADS / 64; ++i) tm = redf[0][i] > tm ? redf[0][i] : tm;
-        thr = tm;
-    }
-    const unsigned long long thrkey = thr < __builtin_inff() ? (((unsigned long long)__float_as_uint(thr) << 32) | 0xFFFFFFFFull) : KEY_MAX;
-    const float vthr = thr < __builtin_inff() ? thr * (1.0f + 32.0f * 5.9604645e-8f) : thr;
-    // ---- B + C: listed videos, SQS_LIST at a time ----
-    for (int vbase = 0; vbase < Nv; ) {
-        __syncthreads();
-        if (tid == 0) s_nlist = 0;
-        __syncthreads();
-        // fill the list from vbase on; stop at the chunk of SQS_THREADS videos that would overflow it
-        int vend = vbase;
-        while (vend < Nv) {
-            const int v = vend + tid;
-            const bool sel = v < Nv && dq[v] <= vthr;
-            if (sel) { const int slot = atomicAdd(&s_nlist, 1); if (slot < SQS_LIST) vlist[slot] = v; }
-            vend += SQS_THREADS;
-            __syncthreads();
-            if (s_nlist + SQS_THREADS > SQS_LIST) break;                     // uniform: the next chunk might not fit
-            __syncthreads();
-        }
-        __syncthreads();
-        const int nlist = s_nlist < SQS_LIST ? s_nlist : SQS_LIST;          // (never exceeds: checked before every chunk)
-        for (int it = tid; it < nlist * SMALLQ_CLIPS_MAX; it += SQS_THREADS) {
-            const int v = vlist[it / SMALLQ_CLIPS_MAX], s0 = it % SMALLQ_CLIPS_MAX;
-            const int c0 = clip_off[v], n = clip_off[v + 1] - c0;
-            if (s0 >= n) continue;
-            const int64_t m0 = mom_off[v];
-            const float *dv = dist + (int64_t)q * total_clips + c0;
-            float sum = 0.0f;
-            for (int e = s0; e < n; ++e) {
-                const float de = dv[e];
-                sum = e == s0 ? de : sum + de;
-                const float sc = sum / (float)(e - s0 + 1);
-                const unsigned long long key = make_key(sc, (unsigned)(id_base + m0 + moment_index(n, s0, e)));
-                if (key <= thrkey) cq[atomicAdd(&s_ncand, 1)] = key;
-            }
-        }
-        vbase = vend < Nv ? vend : Nv;
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (wv != 0) return;
-    // ---- D: wave 0 selects the k best of the candidates ----
-    const int64_t total = s_ncand;
-    unsigned long long key[KPL];
-    unsigned long long pthr = KEY_MAX;
-    int fill = 0;
-    auto lds_sync = [&]() { __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_wave_barrier(); };
-    auto sort_pool = [&](bool final_pass) {
-        lds_sync();
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) { const int e = i * 64 + lane; key[i] = e < fill ? pool[e] : KEY_MAX; }
-        wave_sort<KPL>(key, lane);
-        if (final_pass) return;
-        lds_sync();
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) { const int e = i * 64 + lane; if (e < k) pool[e] = key[i]; }
-        if (fill >= k) pthr = key_at<KPL>(key, k - 1);
-        fill = fill < k ? fill : k;
-    };
-    for (int64_t done = 0; done < total; done += CAP) {
-        unsigned long long x[KPL];
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) {
-            const int64_t gi = done + i * 64 + lane;
-            const unsigned long long vv = cq[gi < total ? gi : total - 1];
-            x[i] = gi < total ? vv : KEY_MAX;
-        }
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) {
-            if (fill + 64 > CAP) sort_pool(false);
-            const bool pass = x[i] < pthr;
-            const unsigned long long m = __ballot(pass);
-            if (pass) pool[fill + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = x[i];
-            fill += __builtin_popcountll(m);
-        }
-    }
-    sort_pool(true);
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        const int e = i * 64 + lane;
-        if (e < k) {
-            const bool ok = key[i] != KEY_MAX;
-            out_dist[(int64_t)q * k + e] = ok ? __uint_as_float((unsigned)(key[i] >> 32)) : __builtin_inff();
-            out_idx[(int64_t)q * k + e] = ok ? (int64_t)(key[i] & 0xffffffffull) : -1;
-        }
-    }
-}
-
-constexpr int SMALLQ_MAX = 64, SMALLQ_CLIPS = SMALLQ_CLIPS_MAX;
-struct SmallqWs { float *dist; unsigned long long *keys, *bufa, *bufb; float *dmin; int64_t Mpad, P0, P1; size_t total; };
-constexpr int SQ_F1 = 20, SQ_F = 32;        // lists of k per first-level range; fan-in of the later levels
-static SmallqWs carve_smallq(void *base, int64_t Nq, int total_clips, int k)
-{
-    SmallqWs w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *p = static_cast<char *>(base) + off; off += align_up(bytes, 256); return p; };
-    const int64_t Mb = (int64_t)total_clips * (SMALLQ_CLIPS + 1) / 2 + 1;            // >= total moments when every video has <= 21 clips
-    w.dist = reinterpret_cast<float *>(take((size_t)Nq * total_clips * 4));
-    if (k > 0) {
-        w.P0 = cdiv(Mb, k);                                                           // the key array as lists of k
-        w.Mpad = w.P0 * k;
-        w.P1 = cdiv(w.P0, SQ_F1);
-        w.keys = reinterpret_cast<unsigned long long *>(take((size_t)Nq * w.Mpad * 8));
-        w.bufa = reinterpret_cast<unsigned long long *>(take((size_t)Nq * w.P1 * k * 8));
-        w.bufb = reinterpret_cast<unsigned long long *>(take((size_t)Nq * cdiv(w.P1, SQ_F) * k * 8));
-        w.dmin = reinterpret_cast<float *>(take((size_t)Nq * total_clips * 4));           // (Nv <= total_clips)
-    }
-    w.total = off;
+    MfmaWs w = carve_mfma(base, 1, 1, total_clips, 0);
+    w.mean_minmax = nullptr; w.bankc = nullptr;
     return w;
 }
-static bool smallq_applicable(int64_t Nq, int Nv, int total_clips, int max_clips, int num_rank, int k)
+
+void bank_prepass(MfmaWs &mw, const float *V, const int32_t *clip_offsets, int Nv, int total_clips, int D, float eps, bool bank_ready,
+                  bool bf16, bool i8, hipStream_t st)
 {
-    const int lim = opt_score_smallq() < SMALLQ_MAX ? opt_score_smallq() : SMALLQ_MAX;
-    return Nq > 0 && Nq <= lim && Nv > 0 && total_clips > 0 && max_clips <= SMALLQ_CLIPS && num_rank <= MAX_RANK && k <= 448;
+    // mean, centred rows, squared norms, the largest norm (bf16: the rounded copy) -- recomputed unless the caller claims
+    // BANK_READY AND the bank still hashes to the signature stored with the products (score_mfma.h)
+    BankSig now{};
+    now.total_clips = total_clips; now.Nv = Nv; now.D = D; now.eps_bits = __builtin_bit_cast(unsigned, eps); now.has_bf16 = bf16 ? 1 : 0;
+    now.has_i8 = i8 ? 1 : 0;
+    const int64_t nwords = (int64_t)total_clips * D;
+    int hb = (int)cdiv(nwords, 256 * 4 * 8);
+    hb = hb < 1 ? 1 : (hb > 2048 ? 2048 : hb);
+    hipLaunchKernelGGL(mfma_bank_hash_kernel, dim3((unsigned)hb), dim3(256), 0, st, reinterpret_cast<const unsigned *>(V), nwords,
+                       reinterpret_cast<const unsigned *>(clip_offsets), (int64_t)Nv + 1, mw.hash_now);
+    hipLaunchKernelGGL(mfma_bank_check_kernel, dim3(1), dim3(1), 0, st, mw.hash_now, now, bank_ready ? 1 : 0, mw.sig, mw.stale, mw.rv, mw.bankc);
+    hipLaunchKernelGGL(mfma_mean_partial_kernel, dim3((unsigned)mw.mean_blocks), dim3(1024), 0, st, V, total_clips, D, mw.mean_rows,
+                       mw.mean_partial, mw.stale, i8 ? mw.mean_minmax : nullptr);
+    hipLaunchKernelGGL(mfma_mean_final_kernel, dim3(1), dim3(1024), 0, st, mw.mean_partial, mw.mean_blocks, D, total_clips, mw.mu, mw.stale,
+                       i8 ? mw.mean_minmax : nullptr, i8 ? mw.bankc : nullptr);
+    if (i8)
+        hipLaunchKernelGGL(mfma_prep_v_i8_kernel, dim3((unsigned)cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps,
+                           mw.mu, mw.vl, mw.va, mw.rv, mw.bankc, mw.stale);
+    else
+        hipLaunchKernelGGL(mfma_prep_v_kernel, dim3((unsigned)cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps,
+                           mw.mu, mw.vc, mw.va, mw.rv, bf16 ? mw.vb : nullptr, mw.stale);
 }
-static int run_smallq(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv,
-                      int total_clips, int max_clips, int D, float eps, int64_t id_base, int k, float *out_dist, int64_t *out_idx, int num_rank,
-                      const float *rank_dist, const int64_t *rank_idx, int64_t *count_lt, void *workspace, vfr_stream_t stream);
+
+int vtk_prepass(MfmaWs &mw, float *qc, float4 *qmeta, const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets,
+                int Nv, int total_clips, int D, float eps, bool bank_ready, hipStream_t st)
+{
+    ProfScope prof(SITE_SCORE_PREP, st);
+    {
+        const FillJob jobs[1] = {{mw.zero_base, nullptr, (size_t)(reinterpret_cast<char *>(mw.stale) - static_cast<char *>(mw.zero_base)) + 4, 0u}};
+        if (int rc = fill_regions(jobs, 1, st)) return rc;
+    }
+    bank_prepass(mw, V, clip_offsets, Nv, total_clips, D, eps, bank_ready, false, false, st);
+    hipLaunchKernelGGL(mfma_prep_q_kernel, dim3((unsigned)cdiv(Nq, 16)), dim3(256), 0, st, Q, Nq, D, eps, mw.mu, qc, mw.rv,
+                       0, (const float *)nullptr, qmeta);
+    VFR_CHECK_LAUNCH("video top-k pre-pass");
+    return VFR_OK;
+}
 
 }  // namespace vfr
 
@@ -2103,7 +1331,7 @@ size_t vfr_score_topk_mfma_workspace_bytes(int64_t Nq, int Nv, int total_clips, 
 {
     if (Nq < 0 || Nv < 0 || k < 0 || total_clips < 0) return 0;
     const size_t a = vfr::carve_mfma(nullptr, Nq, Nv, total_clips, k).total, b = vfr_score_topk_workspace_bytes(Nq, Nv, k);
-    const size_t c = Nq <= vfr::SMALLQ_MAX ? vfr::carve_smallq(nullptr, Nq, total_clips, k).total : 0;
+    const size_t c = vfr::smallq_workspace_bytes(Nq, total_clips, k);
     return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
@@ -2211,30 +1439,7 @@ int vfr_score_topk_mfma(const float *Q, int64_t Nq, const float *V, const int32_
     m.hist = (k > 0 && vfr::opt_score_hist()) ? mw.hist : nullptr; m.hrange = mw.hrange;
     {
         vfr::ProfScope prof(vfr::SITE_SCORE_PREP, st);
-        {
-            // bank side: mean, centred rows, squared norms, the largest norm (bf16: the rounded copy) -- recomputed unless the
-            // caller claims BANK_READY AND the bank still hashes to the signature stored with the products (score_mfma.h)
-            vfr::BankSig now{};
-            now.total_clips = total_clips; now.Nv = Nv; now.D = D; now.eps_bits = __builtin_bit_cast(unsigned, eps); now.has_bf16 = bf16 ? 1 : 0;
-            now.has_i8 = i8 ? 1 : 0;
-            const int64_t nwords = (int64_t)total_clips * D;
-            int hb = (int)vfr::cdiv(nwords, 256 * 4 * 8);
-            hb = hb < 1 ? 1 : (hb > 2048 ? 2048 : hb);
-            hipLaunchKernelGGL(vfr::mfma_bank_hash_kernel, dim3((unsigned)hb), dim3(256), 0, st, reinterpret_cast<const unsigned *>(V), nwords,
-                               reinterpret_cast<const unsigned *>(clip_offsets), (int64_t)Nv + 1, mw.hash_now);
-            hipLaunchKernelGGL(vfr::mfma_bank_check_kernel, dim3(1), dim3(1), 0, st, mw.hash_now, now, bank_ready ? 1 : 0, mw.sig, mw.stale, mw.rv,
-                               mw.bankc);
-            hipLaunchKernelGGL(vfr::mfma_mean_partial_kernel, dim3((unsigned)mw.mean_blocks), dim3(1024), 0, st, V, total_clips, D, mw.mean_rows,
-                               mw.mean_partial, mw.stale, i8 ? mw.mean_minmax : nullptr);
-            hipLaunchKernelGGL(vfr::mfma_mean_final_kernel, dim3(1), dim3(1024), 0, st, mw.mean_partial, mw.mean_blocks, D, total_clips, mw.mu, mw.stale,
-                               i8 ? mw.mean_minmax : nullptr, i8 ? mw.bankc : nullptr);
-            if (i8)
-                hipLaunchKernelGGL(vfr::mfma_prep_v_i8_kernel, dim3((unsigned)vfr::cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps,
-                                   mw.mu, mw.vl, mw.va, mw.rv, mw.bankc, mw.stale);
-            else
-                hipLaunchKernelGGL(vfr::mfma_prep_v_kernel, dim3((unsigned)vfr::cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps,
-                                   mw.mu, mw.vc, mw.va, mw.rv, bf16 ? mw.vb : nullptr, mw.stale);
-        }
+        vfr::bank_prepass(mw, V, clip_offsets, Nv, total_clips, D, eps, bank_ready, bf16, i8, st);
         if (i8)
             hipLaunchKernelGGL(vfr::mfma_prep_q_i8_kernel, dim3((unsigned)vfr::cdiv(Nq, 64)), dim3(1024), 0, st, Q, Nq, D, eps, mw.mu, mw.ql, mw.rv,
                                mw.bankc, num_rank, rank_dist, mw.qmeta, mw.qf, mw.qdbg, mw.qscale);
@@ -2255,12 +1460,9 @@ int vfr_score_topk_mfma(const float *Q, int64_t Nq, const float *V, const int32_
         }
         VFR_CHECK_LAUNCH("mfma pre-pass");
     }
-    vfr::ScoreArgs a{};
-    a.Q = Q; a.Nq = Nq; a.V = V; a.clip_off = clip_offsets; a.mom_off = moment_offsets; a.Nv = Nv; a.D = D; a.eps = eps;
-    a.id_base = id_base; a.k = kp; a.num_rank = num_rank; a.rank_dist = rank_dist; a.rank_idx = rank_idx; a.count_lt = count_lt;
-    a.ds_rows = max_clips < 1 ? 1 : max_clips;
-    a.total_clips = total_clips;
-    a.min_clips = min_clips;
+    // the pre-filter's pass keeps k' = k + MF_EXTRA candidates by approximate key
+    vfr::ScoreArgs a = vfr::pass_args(Q, Nq, V, clip_offsets, moment_offsets, Nv, total_clips, min_clips, max_clips, D, eps, id_base, kp,
+                                      num_rank, rank_dist, rank_idx, count_lt);
     a.mf_host = &m; a.mf_bf16 = bf16 ? 1 : 0; a.mf_i8 = i8 ? 1 : 0;
     if (int rc = vfr::run_pass(a, w, thr_seed != nullptr, nullptr, nullptr, kp > 0 ? w.pre_keys : nullptr, st)) return rc;
     int g, c;
@@ -2300,10 +1502,9 @@ int vfr_score_topk_mfma(const float *Q, int64_t Nq, const float *V, const int32_
     if (bf16) return unsort();
     // ---- flagged query groups: the exact kernels, every launch limited to them (returns at once when nothing is flagged) ----
     vfr::TopkWs wx = vfr::carve_topk(mw.topk, Nq, Nv, k);
-    vfr::ScoreArgs x{};
-    x.Q = Q; x.Nq = Nq; x.V = V; x.clip_off = clip_offsets; x.mom_off = moment_offsets; x.Nv = Nv; x.D = D; x.eps = eps;
-    x.id_base = id_base; x.k = k; x.num_rank = num_rank; x.rank_dist = rank_dist; x.rank_idx = rank_idx; x.count_lt = count_lt;
-    x.ds_rows = max_clips < 1 ? 1 : max_clips; x.total_clips = total_clips; x.min_clips = min_clips;
+    // (the exact pass: the caller's k instead of k', the fallback mask and its own profiler site)
+    vfr::ScoreArgs x = vfr::pass_args(Q, Nq, V, clip_offsets, moment_offsets, Nv, total_clips, min_clips, max_clips, D, eps, id_base, k,
+                                      num_rank, rank_dist, rank_idx, count_lt);
     x.group_mask = mw.fallback;
     x.prof_site = vfr::SITE_SCORE_FALLBACK;
     if (k > 0) {
@@ -2340,118 +1541,6 @@ int vfr_score_topk_mfma_stats(const void *workspace, int64_t Nq, int Nv, int tot
             fprintf(stderr, "[mfma] tab[%d] LOX %08x HIX %08x LOW %08x width %u  (lo sum %.7g)\n", i, tab[4 * i], tab[4 * i + 1], tab[4 * i + 2],
                     tab[4 * i + 3], __builtin_bit_cast(float, tab[4 * i] - 1u));
     }
-    return VFR_OK;
-}
-
-static int launch_merge_parts(const float *pd, const int64_t *pi, bool packed, int G, int64_t Nq, int k, float *od,
-                              int64_t *oi, int64_t *okeys, vfr_stream_t stream, int64_t slot_stride = 0, int64_t q_stride = 0)
-{
-    if (slot_stride == 0) slot_stride = Nq * k;
-    if (q_stride == 0) q_stride = k;
-    dim3 grid((unsigned)vfr::cdiv(Nq, 4)), block(256);
-    const int kpl = vfr::kpl_for(k);
-    vfr::ProfScope prof(vfr::SITE_EXCHANGE, vfr::as_stream(stream));
-#define VFR_MERGE(KPL, PACKED) hipLaunchKernelGGL((vfr::topk_merge_parts_kernel<KPL, PACKED>), grid, block, 0, \
-                                                  vfr::as_stream(stream), pd, pi, slot_stride, q_stride, G, Nq, k, od, oi, okeys)
-    if (packed) { if (kpl == 4) VFR_MERGE(4, true); else VFR_MERGE(8, true); }
-    else        { if (kpl == 4) VFR_MERGE(4, false); else VFR_MERGE(8, false); }
-#undef VFR_MERGE
-    VFR_CHECK_LAUNCH("topk_merge_parts_kernel");
-    return VFR_OK;
-}
-
-int vfr_topk_merge_f32(const float *part_dist, const int64_t *part_idx, int G, int64_t Nq, int k, float *out_dist,
-                       int64_t *out_idx, vfr_stream_t stream)
-{
-    VFR_REQUIRE(part_dist && part_idx && out_dist && out_idx && G > 0 && Nq >= 0 && k > 0, VFR_EINVAL,
-                "vfr_topk_merge_f32: bad argument");
-    VFR_REQUIRE(k <= 448, VFR_EUNSUPPORTED, "vfr_topk_merge_f32: k=%d > 448", k);
-    VFR_REQUIRE((int64_t)G * k < (1ll << 31), VFR_EUNSUPPORTED, "vfr_topk_merge_f32: G*k too large");
-    if (Nq == 0) return VFR_OK;
-    return launch_merge_parts(part_dist, part_idx, false, G, Nq, k, out_dist, out_idx, nullptr, stream);
-}
-
-int vfr_topk_pack_keys(const float *dist, const int64_t *idx, int64_t n, int64_t *keys, vfr_stream_t stream)
-{
-    VFR_REQUIRE(n >= 0 && (n == 0 || (dist && idx && keys)), VFR_EINVAL, "vfr_topk_pack_keys: bad argument");
-    if (n == 0) return VFR_OK;
-    vfr::ProfScope prof(vfr::SITE_EXCHANGE, vfr::as_stream(stream));
-    hipLaunchKernelGGL(vfr::topk_pack_keys_kernel, dim3((unsigned)vfr::cdiv(n, 256)), dim3(256), 0,
-                       vfr::as_stream(stream), dist, idx, n, keys);
-    VFR_CHECK_LAUNCH("topk_pack_keys_kernel");
-    return VFR_OK;
-}
-
-int vfr_topk_merge_keys_strided(const int64_t *part_keys, int64_t slot_stride, int G, int64_t Nq, int k, float *out_dist,
-                                int64_t *out_idx, int64_t *out_keys, vfr_stream_t stream)
-{
-    VFR_REQUIRE(part_keys && G > 0 && Nq >= 0 && k > 0 && ((out_dist && out_idx) || out_keys) &&
-                (out_dist == nullptr) == (out_idx == nullptr) && slot_stride >= Nq * k, VFR_EINVAL,
-                "vfr_topk_merge_keys: bad argument");
-    VFR_REQUIRE(k <= 448, VFR_EUNSUPPORTED, "vfr_topk_merge_keys: k=%d > 448", k);
-    VFR_REQUIRE((int64_t)G * k < (1ll << 31), VFR_EUNSUPPORTED, "vfr_topk_merge_keys: G*k too large");
-    if (Nq == 0) return VFR_OK;
-    return launch_merge_parts(nullptr, part_keys, true, G, Nq, k, out_dist, out_idx, out_keys, stream, slot_stride);
-}
-
-int vfr_topk_merge_keys(const int64_t *part_keys, int G, int64_t Nq, int k, float *out_dist, int64_t *out_idx,
-                        int64_t *out_keys, vfr_stream_t stream)
-{
-    return vfr_topk_merge_keys_strided(part_keys, Nq * k, G, Nq, k, out_dist, out_idx, out_keys, stream);
-}
-
-int vfr_gt_best_keys_f32(const float *own_scores, int64_t n_sel, int M, int score_stride, const uint8_t *labels, int R,
-                         int label_stride, const int64_t *id_base, const int64_t *sel, int64_t Nq, int64_t *keys,
-                         vfr_stream_t stream)
-{
-    VFR_REQUIRE(keys && R > 0 && Nq >= 0 && n_sel >= 0 && M >= 0 && score_stride >= M && label_stride >= M, VFR_EINVAL,
-                "vfr_gt_best_keys_f32: bad argument");
-    VFR_REQUIRE(n_sel == 0 || (own_scores && labels && id_base && sel), VFR_EINVAL, "vfr_gt_best_keys_f32: null input");
-    if (Nq == 0) return VFR_OK;
-    vfr::ProfScope prof(vfr::SITE_EXCHANGE, vfr::as_stream(stream));
-    hipLaunchKernelGGL(vfr::gt_fill_keys_kernel, dim3((unsigned)vfr::cdiv((int64_t)R * Nq, 256)), dim3(256), 0,
-                       vfr::as_stream(stream), (int64_t)R * Nq, keys);
-    VFR_CHECK_LAUNCH("gt_fill_keys_kernel");
-    if (n_sel == 0) return VFR_OK;
-    hipLaunchKernelGGL(vfr::gt_best_keys_kernel, dim3((unsigned)vfr::cdiv(n_sel, 4)), dim3(256), 0, vfr::as_stream(stream),
-                       own_scores, n_sel, M, score_stride, labels, R, label_stride, id_base, sel, Nq, keys);
-    VFR_CHECK_LAUNCH("gt_best_keys_kernel");
-    return VFR_OK;
-}
-
-int vfr_gt_rank_keys_f32(const float *own_scores, int64_t n_sel, int M, int score_stride, const uint8_t *labels, int R,
-                         int label_stride, const int64_t *id_base, const int64_t *sel, int64_t Nq, int64_t *keys,
-                         float *rank_dist, int64_t *rank_idx, int64_t *count_zero, int *missing, vfr_stream_t stream)
-{
-    VFR_REQUIRE(keys && R > 0 && Nq >= 0 && n_sel >= 0 && M >= 0 && score_stride >= M && label_stride >= M, VFR_EINVAL,
-                "vfr_gt_rank_keys_f32: bad argument");
-    VFR_REQUIRE(n_sel == 0 || (own_scores && labels && id_base && sel), VFR_EINVAL, "vfr_gt_rank_keys_f32: null input");
-    VFR_REQUIRE((rank_dist == nullptr) == (rank_idx == nullptr), VFR_EINVAL, "vfr_gt_rank_keys_f32: rank_dist and rank_idx go together");
-    if (Nq == 0) return VFR_OK;
-    vfr::ProfScope prof(vfr::SITE_EXCHANGE, vfr::as_stream(stream));
-    hipLaunchKernelGGL(vfr::gt_fill_rank_kernel, dim3((unsigned)vfr::cdiv((int64_t)R * Nq, 256)), dim3(256), 0, vfr::as_stream(stream),
-                       (int64_t)R * Nq, keys, rank_dist, rank_idx, count_zero, missing);
-    VFR_CHECK_LAUNCH("gt_fill_rank_kernel");
-    if (n_sel == 0) return VFR_OK;
-    hipLaunchKernelGGL(vfr::gt_best_keys_kernel, dim3((unsigned)vfr::cdiv(n_sel, 4)), dim3(256), 0, vfr::as_stream(stream),
-                       own_scores, n_sel, M, score_stride, labels, R, label_stride, id_base, sel, Nq, keys, rank_dist, rank_idx, missing);
-    VFR_CHECK_LAUNCH("gt_best_keys_kernel");
-    return VFR_OK;
-}
-
-int vfr_gt_labels_u8(const int32_t *times, const int32_t *nannot, const int32_t *n_own, int64_t Nq, int A,
-                     const double *thresholds_host, int R, int strict, int Mmax, uint8_t *labels, vfr_stream_t stream)
-{
-    VFR_REQUIRE(Nq >= 0 && A >= 0 && Mmax >= 0 && R > 0 && thresholds_host, VFR_EINVAL, "vfr_gt_labels_u8: bad argument");
-    VFR_REQUIRE(R <= vfr::MAX_LABEL_THR, VFR_EUNSUPPORTED, "vfr_gt_labels_u8: R=%d > %d thresholds", R, vfr::MAX_LABEL_THR);
-    if (Nq == 0 || Mmax == 0) return VFR_OK;
-    VFR_REQUIRE(times && nannot && n_own && labels, VFR_EINVAL, "vfr_gt_labels_u8: null pointer");
-    vfr::LabelThr t{};
-    for (int r = 0; r < R; ++r) t.t[r] = thresholds_host[r];
-    vfr::ProfScope prof(vfr::SITE_EXCHANGE, vfr::as_stream(stream));
-    hipLaunchKernelGGL(vfr::gt_labels_kernel, dim3((unsigned)vfr::cdiv(Nq * Mmax, 256)), dim3(256), 0, vfr::as_stream(stream),
-                       times, nannot, n_own, Nq, A, R, t, strict, Mmax, labels);
-    VFR_CHECK_LAUNCH("gt_labels_kernel");
     return VFR_OK;
 }
 
@@ -2540,80 +1629,6 @@ __global__ __launch_bounds__(64) void score_i8_debug_kernel(const signed char *_
         }
     }
 }
-static int run_smallq(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv,
-                      int total_clips, int max_clips, int D, float eps, int64_t id_base, int k, float *out_dist, int64_t *out_idx, int num_rank,
-                      const float *rank_dist, const int64_t *rank_idx, int64_t *count_lt, void *workspace, vfr_stream_t stream)
-{
-    hipStream_t st = as_stream(stream);
-    SmallqWs w = carve_smallq(workspace, Nq, total_clips, k);
-    {
-        ProfScope prof(SITE_SCORE_FUSED, st);
-        const dim3 grid((unsigned)cdiv(total_clips, 256));
-        // eight queries per pass over the bank (sixteen were measured: 0.574 against 0.542 ms at 64 queries, 0.194 against 0.184 at
-        // 16 -- the kernel is bound by its 3 VALU issues per (query, clip, dimension), not by the row reads, and the wider
-        // form's registers cost a wave of occupancy)
-        {
-            const dim3 g8(grid.x, (unsigned)cdiv(Nq, 8));
-            if (Nq == 1)      hipLaunchKernelGGL(smallq_dist_kernel<1>, grid, dim3(256), 0, st, Q, (int)Nq, V, total_clips, D, eps, w.dist);
-            else if (Nq == 2) hipLaunchKernelGGL(smallq_dist_kernel<2>, grid, dim3(256), 0, st, Q, (int)Nq, V, total_clips, D, eps, w.dist);
-            else if (Nq <= 4) hipLaunchKernelGGL(smallq_dist_kernel<4>, grid, dim3(256), 0, st, Q, (int)Nq, V, total_clips, D, eps, w.dist);
-            else              hipLaunchKernelGGL(smallq_dist_kernel<8>, g8, dim3(256), 0, st, Q, (int)Nq, V, total_clips, D, eps, w.dist);
-        }
-        // top-k by video selection (smallq_select_kernel) unless switched off: then the key array + selection tree
-        const bool select = k > 0 && opt_score_smallq_select();
-        // unwritten key slots (the padding past the last moment) must read as empty: any value >= KEY_EMPTY does
-        if (k > 0 && !select && hipMemsetAsync(w.keys, 0xFF, (size_t)Nq * w.Mpad * 8, st) != hipSuccess)
-            return fail(VFR_EHIP, "vfr_score_topk_mfma: hipMemsetAsync failed");
-        if (select && opt_score_smallq_rank() > 0 && Nq >= opt_score_smallq_rank()) {
-            // video-selection form: no key array -- rank counts and the per-video smallest distance with lane = video
-            const dim3 rgrid((unsigned)cdiv(Nv, 64), (unsigned)Nq);
-#define VFR_SQR(NTV, NRV) hipLaunchKernelGGL((smallq_rank_kernel<NTV, NRV>), rgrid, dim3(64), 0, st, w.dist, (int)Nq, clip_offsets, moment_offsets, Nv, total_clips, \
-                                             id_base, num_rank, rank_dist, rank_idx, count_lt, w.dmin)
-            if (max_clips <= 6) { if (num_rank <= 2) VFR_SQR(6, 2); else VFR_SQR(6, MAX_RANK); }
-            else                { if (num_rank <= 2) VFR_SQR(SMALLQ_CLIPS_MAX, 2); else VFR_SQR(SMALLQ_CLIPS_MAX, MAX_RANK); }
-#undef VFR_SQR
-        } else
-        if (k > 0 || num_rank > 0)
-            hipLaunchKernelGGL(smallq_moments_kernel, dim3((unsigned)cdiv(Nv, SQ_VIDEOS), (unsigned)Nq), dim3(256), 0, st, w.dist, (int)Nq, clip_offsets,
-                               moment_offsets, Nv, total_clips, id_base, (k > 0 && !select) ? w.keys : nullptr, w.Mpad, num_rank, rank_dist, rank_idx,
-                               count_lt, select ? w.dmin : nullptr);
-        VFR_CHECK_LAUNCH("smallq kernels");
-    }
-    {
-        const bool select = k > 0 && opt_score_smallq_select();
-        if (select) {
-            ProfScope prof2(SITE_TOPK_MERGE, st);
-            if (kpl_for(k) == 4)
-                hipLaunchKernelGGL(smallq_select_kernel<4>, dim3((unsigned)Nq), dim3(SQS_THREADS), 0, st, w.dist, w.dmin, clip_offsets, moment_offsets,
-                                   Nv, total_clips, id_base, k, w.keys, w.Mpad, out_dist, out_idx);
-            else
-                hipLaunchKernelGGL(smallq_select_kernel<8>, dim3((unsigned)Nq), dim3(SQS_THREADS), 0, st, w.dist, w.dmin, clip_offsets, moment_offsets,
-                                   Nv, total_clips, id_base, k, w.keys, w.Mpad, out_dist, out_idx);
-            VFR_CHECK_LAUNCH("smallq_select_kernel");
-            return VFR_OK;
-        }
-    }
-    if (k == 0) return VFR_OK;
-    // selection tree: ranges of SQ_F1 lists of k keys -> lists of k, then SQ_F lists at a time until one list per query is left
-    ProfScope prof(SITE_TOPK_MERGE, st);
-    const int kpl = kpl_for(k);
-    const unsigned long long *in = w.keys;
-    int64_t Pin = w.P0;
-    int F = SQ_F1;
-    unsigned long long *bufs[2] = {w.bufa, w.bufb};
-    for (int level = 0;; ++level) {
-        const int64_t Pout = cdiv(Pin, F), n_vq = Nq * Pout;
-        const bool root = Pout == 1;
-        unsigned long long *out = root ? nullptr : bufs[level & 1];
-        const dim3 grid((unsigned)cdiv(n_vq, 4));
-        if (kpl == 4) hipLaunchKernelGGL(topk_tree_kernel<4>, grid, dim3(256), 0, st, in, Pin, F, Pout, n_vq, k, out, root ? out_dist : nullptr, root ? out_idx : nullptr);
-        else          hipLaunchKernelGGL(topk_tree_kernel<8>, grid, dim3(256), 0, st, in, Pin, F, Pout, n_vq, k, out, root ? out_dist : nullptr, root ? out_idx : nullptr);
-        if (root) break;
-        in = out; Pin = Pout; F = Pin <= 2 * SQ_F ? (int)Pin : SQ_F;
-    }
-    VFR_CHECK_LAUNCH("topk_tree_kernel");
-    return VFR_OK;
-}
 }  // namespace vfr
 
 extern "C" int vfr_mfma_selfcheck(const float *A, const float *B, int K, int reversed, int *mismatches, vfr_stream_t stream)
@@ -2650,21 +1665,8 @@ extern "C" int vfr_score_i8_debug(const float *Q, int64_t Nq, const float *V, co
     hipStream_t st = vfr::as_stream(stream);
     vfr::MfmaWs mw = vfr::carve_mfma(workspace, Nq, Nv, total_clips, 0);
     if (int rc = vfr::fill_region(mw.zero_base, 0u, mw.zero_bytes, st)) return rc;
-    vfr::BankSig now{};
-    now.total_clips = total_clips; now.Nv = Nv; now.D = D; now.eps_bits = __builtin_bit_cast(unsigned, eps); now.has_i8 = 1;
-    const int64_t nwords = (int64_t)total_clips * D;
-    int hb = (int)vfr::cdiv(nwords, 256 * 4 * 8);
-    hb = hb < 1 ? 1 : (hb > 2048 ? 2048 : hb);
     const int groups = (int)vfr::cdiv(Nq, 64);
-    hipLaunchKernelGGL(vfr::mfma_bank_hash_kernel, dim3((unsigned)hb), dim3(256), 0, st, reinterpret_cast<const unsigned *>(V), nwords,
-                       reinterpret_cast<const unsigned *>(clip_offsets), (int64_t)Nv + 1, mw.hash_now);
-    hipLaunchKernelGGL(vfr::mfma_bank_check_kernel, dim3(1), dim3(1), 0, st, mw.hash_now, now, 0, mw.sig, mw.stale, mw.rv, mw.bankc);
-    hipLaunchKernelGGL(vfr::mfma_mean_partial_kernel, dim3((unsigned)mw.mean_blocks), dim3(1024), 0, st, V, total_clips, D, mw.mean_rows,
-                       mw.mean_partial, mw.stale, mw.mean_minmax);
-    hipLaunchKernelGGL(vfr::mfma_mean_final_kernel, dim3(1), dim3(1024), 0, st, mw.mean_partial, mw.mean_blocks, D, total_clips, mw.mu, mw.stale,
-                       mw.mean_minmax, mw.bankc);
-    hipLaunchKernelGGL(vfr::mfma_prep_v_i8_kernel, dim3((unsigned)vfr::cdiv(total_clips, 4)), dim3(256), 0, st, V, total_clips, D, eps, mw.mu,
-                       mw.vl, mw.va, mw.rv, mw.bankc, mw.stale);
+    vfr::bank_prepass(mw, V, clip_offsets, Nv, total_clips, D, eps, false, false, true, st);
     hipLaunchKernelGGL(vfr::mfma_prep_q_i8_kernel, dim3((unsigned)groups), dim3(1024), 0, st, Q, Nq, D, eps, mw.mu, mw.ql, mw.rv, mw.bankc, 0,
                        (const float *)nullptr, mw.qmeta, mw.qf, mw.qdbg, mw.qscale);
     hipLaunchKernelGGL(vfr::score_i8_debug_kernel, dim3((unsigned)groups, (unsigned)vfr::cdiv(total_clips, 16)), dim3(64), 0, st, mw.ql, mw.vl,
@@ -2678,12 +1680,3 @@ extern "C" int vfr_score_i8_debug(const float *Q, int64_t Nq, const float *V, co
         if (hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return vfr::fail(VFR_EHIP, "vfr_score_i8_debug: copy failed");
     return VFR_OK;
 }
-
-// video-level retrieval: top-k distinct videos and video rank counts (reuses the pre-filter's bank-side pre-passes above)
-#include "video_topk.h"
-
-// diversified moment retrieval: per-video cap and temporal NMS over the video top-k above
-#include "moment_nms.h"
-
-// paragraph-to-video retrieval: groups of sentences against the video bounds / exact triangles above
-#include "paragraphs.h"

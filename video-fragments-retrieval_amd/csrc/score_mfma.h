@@ -72,7 +72,6 @@ constexpr unsigned MF_WIDTH_MAX = 1u << 28;  // window widths (ulps of the sum) 
 constexpr int MF_HBINS = 32;                 // bins of the top-k threshold histogram (below)
 constexpr int MF_TAB = 4;                    // table words per (query, key, L): LO, HI (exact, exclusive bit bounds), LO wide, width
 #define MF_RING_ROWS(NT) ((NT) > 6 ? 38 : 32)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 // int8 operand mode (see "int8 limbs" above)
 constexpr int I8_XMAX = 127 * 65536 + 127 * 256 + 127;   // |X| <= I8_XMAX <=> three balanced base-256 digits in [-128, 127] hold X

@@ -2,7 +2,7 @@
 //
 // Semantics are those of the full-corpus entry points restricted to a per-query list of videos: key = (fp32 distance, global
 // moment id) ascending, id = id_base + mom_off[v] + j (j = position in utils.generate_moments(n_v)), the best key of a video is
-// the smallest key over its WHOLE triangle (csrc/video_topk.h explains why the triangle is needed).  Lists are CSR over queries
+// the smallest key over its WHOLE triangle (csrc/video_topk.hip explains why the triangle is needed).  Lists are CSR over queries
 // (cand_off [Nq+1] int64, cand_vid [nnz] int32, corpus-global video indices, strictly ascending per query); entries outside
 // [vid_base, vid_base + Nv) belong to another shard and are skipped, so every shard takes the same lists.
 //
