@@ -95,6 +95,19 @@ int vfr_linear_f32(const float *A, int64_t M, int K, const float *W, const float
  * result is right.  The event is reported through the fault word: vfr_set_fault_word / vfr_poll_faults below.
  * vfr_set_option("lstm_persist", 0) selects one launch per step instead.                                            */
 size_t vfr_bilstm_workspace_bytes(int64_t B, int T, int E, int H, int vocab);
+/* Tests only: byte offset, inside that workspace, of two uint32 counters [forward, reverse].  With option "lstm_live_blocks"
+ * bit 1 set, the fused MFMA steps of a call add the (16-row x 16-unit) blocks they issued matrix work for; the call zeroes
+ * them first.  No output is computed from them.                                                                       */
+size_t vfr_bilstm_debug_offset(int64_t B, int T, int E, int H, int vocab);
+/* Introspection (no device needed): the form the fused BiLSTM steps of `rows` GEMM rows (queries + 1) take under the current
+ * options on a device of `cus` compute units.  *one_launch: 1 = the one-launch kernel is selected ("lstm_multi"), 0 = one launch
+ * per step; *tile: rows per tile as "lstm_tile" numbers them (1 = 64, 2 = 128, 3 = 32); *slots: the one-launch grid (0 otherwise).
+ * A selected one-launch form still falls back to the per-step launches when its grid is not resident at once.
+ * CONSTRAINT of the one-launch form (the default from 2500 rows on): its workgroups wait for each other, so run ONE such encode
+ * per device at a time.  Two concurrent large vfr_bilstm_final_f32 calls, or another process filling the device, can leave each
+ * with part of its grid resident; the waits are bounded (seconds), the batch is then re-encoded by the rescue kernel and the
+ * event reported through the fault word -- results stay right, the call is slow.  "lstm_multi" 0 removes the constraint.  */
+int vfr_lstm_plan(int64_t rows, int H, int T, int cus, int *one_launch, int *tile, int64_t *slots);
 int vfr_bilstm_final_f32(const int64_t *tokens, int64_t B, int T, const float *emb, int vocab, const float *len_tab,
                          const float *Wih_f, const float *Whh_f, const float *bih_f, const float *bhh_f,
                          const float *Wih_b, const float *Whh_b, const float *bih_b, const float *bhh_b, int E,
@@ -695,9 +708,16 @@ int vfr_math_f32(int op, const float *x, const float *y, float *out, int64_t n, 
  * its own kernel), "vgg_direct1" 1|0 (first VGG convolution as the direct kernel | the implicit-GEMM MFMA kernel), "vgg_halo" 1|0 (the VGG stack on
  * halo-padded activations where its shape allows: convolution loader without tap masks | unpadded), "lstm_fast" 1|0 (the
  * select-free instantiation of the table-start LSTM step where the launch qualifies | always the general form),
- * "lstm_multi" 0|1 (EXPERIMENT, default 0: one launch per LSTM step | all T steps of both directions in one launch -- ordered task
- * lists per XCD group, completion counters, agent-scope state traffic; with "lstm_tile" 2: 128-row tiles; a give-up is repaired by a
- * rescue kernel and reported through the fault word like the sequence kernels'),
+ * "lstm_multi" 2|1|0 (all T LSTM steps of both directions in one launch -- ordered task lists per XCD group, completion counters,
+ * agent-scope state traffic: automatic, i.e. from "lstm_multi_min" GEMM rows on (default 2500) at H >= 512 with 128-row tiles while
+ * "lstm_tile" is 0 | always, tile height by "lstm_tile" | never: one launch per step; a give-up is repaired by a
+ * rescue kernel and reported through the fault word like the sequence kernels'; it needs its whole grid resident at once, which
+ * is checked at launch -- occupancy x CUs -- and the per-step launches are taken when it is not; "lstm_multi_taken" is READ-ONLY
+ * (vfr_set_option refuses it) and written by every vfr_bilstm_final_f32: 1 = the call ran the one-launch kernel, 2 = selected but
+ * not resident at once, per-step launches taken, 0 = any other path),
+ * "lstm_live_blocks" 1|0 (fused LSTM step: a wave issues fragment reads, MFMAs, table gather and gate epilogue only for its 16-row
+ * blocks that hold a row below the direction's active count and a unit below H | for every block of its tile -- same bits; +2:
+ * count the issued blocks, see vfr_bilstm_debug_offset),
  * "score_kth_seed" 1|0 (stage A of the top-k threshold ladder takes its seed by bisection on the candidates' score bits | by the merge kernel),
  * "score_smallq_rank" N (few-queries path with video selection: from N queries on -- default 8 -- the rank counts run with lane = video,
  * straight-line triangle, 3-instruction exact quotient; 0: always the 16-threads-per-video moment kernel),

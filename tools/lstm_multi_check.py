@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The multi-step BiLSTM launch (EXPERIMENT `lstm_multi` 1: all T steps in one kernel; with `lstm_tile` 2: 128-row tiles) against one
-launch per step (`lstm_multi` 0, the default): bits and time of the whole query-encoder pass.
+"""The multi-step BiLSTM launch (`lstm_multi` 1: all T steps in one kernel; with `lstm_tile` 2: 128-row tiles, the form the default
+`lstm_multi` 2 takes from 2 500 rows on) against one launch per step (`lstm_multi` 0): bits and time of the whole query-encoder pass.
 
     python tools/lstm_multi_check.py [B ...]      (default: 64 130 313 626 1250 2500 5000)
 """
@@ -23,6 +23,7 @@ def main():
     lstm = {k.split("lstm.")[1]: torch.from_numpy(v).to(dev) for k, v in sd.items() if k.startswith("lstm.")}
     emb = torch.from_numpy(sd["word_embedding.weight"]).to(dev)
     wfc, bfc = torch.from_numpy(sd["lang_fc.weight"]).to(dev), torch.from_numpy(sd["lang_fc.bias"]).to(dev)
+    old = {n: _vfr.get_option(n) for n in ("lstm_multi", "lstm_tile")}
     for B in Bs:
         tokens = torch.from_numpy(synth.query_tokens(B, seed=B)).to(dev)
         row = {}
@@ -38,7 +39,8 @@ def main():
             torch.cuda.synchronize()
             row[multi] = (time.perf_counter() - t0) / n * 1e3
             outs[multi] = out
-        _vfr.set_option("lstm_multi", 0); _vfr.set_option("lstm_tile", 0)
+        for n, v in old.items():
+            _vfr.set_option(n, v)
         same = torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)) and torch.equal(outs[0].view(torch.int32), outs[2].view(torch.int32))
         print(f"B = {B:5d}: per-step launches {row[0]:7.3f} ms   one launch {row[1]:7.3f} ms   one launch, 128-row tiles {row[2]:7.3f} ms   {'IDENTICAL' if same else '*** DIFFERENT ***'}"
               f"   faults {_vfr.poll_faults()}", flush=True)

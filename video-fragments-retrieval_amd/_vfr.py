@@ -40,6 +40,8 @@ SIGNATURES = {
     "vfr_visual_mlp_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
     "vfr_linear_f32": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_bilstm_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    "vfr_bilstm_debug_offset": (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    "vfr_lstm_plan": (_i32, [_i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vfr_bilstm_final_f32": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp] + [_vp] * 8 + [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "vfr_score_moments_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _f32, _vp, _vp]),
     "vfr_score_own_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp]),
@@ -328,8 +330,9 @@ def linear(A, W, b=None, relu: bool = False) -> torch.Tensor:
 _LSTM_NAMES = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
 
 
-def bilstm_final(tokens, emb, lstm: dict, Wfc, bfc, len_tab=None) -> torch.Tensor:
-    """tokens int64 [B,T] -> query embeddings [B,D]  (model/models.py:61-66)."""
+def bilstm_final(tokens, emb, lstm: dict, Wfc, bfc, len_tab=None, workspace=None) -> torch.Tensor:
+    """tokens int64 [B,T] -> query embeddings [B,D]  (model/models.py:61-66).  ``workspace``: a uint8 device tensor to run
+    in when it is large enough (tests read the debug counters out of it: ``lstm_issued_blocks``)."""
     tokens = _dev(tokens, torch.int64, "tokens")
     emb = _dev(emb, torch.float32, "emb")
     ws_ = [_dev(lstm[n], torch.float32, n) for n in _LSTM_NAMES] + \
@@ -342,11 +345,31 @@ def bilstm_final(tokens, emb, lstm: dict, Wfc, bfc, len_tab=None) -> torch.Tenso
     poll_faults()                              # (a give-up of an EARLIER call's sequence kernel: repaired there, reported here)
     out = torch.empty((B, D), dtype=torch.float32, device=tokens.device)
     nbytes = lib().vfr_bilstm_workspace_bytes(B, T, E, H, emb.shape[0])
-    ws = _workspace(None, nbytes, tokens.device)
+    ws = _workspace(workspace, nbytes, tokens.device)
     _check(lib().vfr_bilstm_final_f32(tokens.data_ptr(), B, T, emb.data_ptr(), emb.shape[0], _ptr(lt),
                                       *[w.data_ptr() for w in ws_], E, H, Wfc.data_ptr(), bfc.data_ptr(), D,
                                       out.data_ptr(), ws.data_ptr(), nbytes, _stream()), "vfr_bilstm_final_f32")
     return out
+
+
+def bilstm_workspace(B: int, T: int, E: int, H: int, vocab: int, device) -> torch.Tensor:
+    """A workspace for ``bilstm_final(..., workspace=)`` at this shape."""
+    return torch.empty((max(lib().vfr_bilstm_workspace_bytes(B, T, E, H, vocab), 1),), dtype=torch.uint8, device=device)
+
+
+def lstm_plan(rows: int, H: int, T: int, cus: int):
+    """(one_launch, tile, slots) of the fused BiLSTM steps under the current options (include/vfr.h vfr_lstm_plan; host only)."""
+    one, tile, slots = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    _check(lib().vfr_lstm_plan(rows, H, T, cus, ctypes.addressof(one), ctypes.addressof(tile), ctypes.addressof(slots)), "vfr_lstm_plan")
+    return bool(one.value), tile.value, slots.value
+
+
+def lstm_issued_blocks(workspace: torch.Tensor, B: int, T: int, E: int, H: int, vocab: int):
+    """(forward, reverse) counts of (16-row x 16-unit) MFMA blocks the fused LSTM steps of the last ``bilstm_final`` in
+    ``workspace`` issued (option ``lstm_live_blocks`` bit 1; include/vfr.h vfr_bilstm_debug_offset).  Synchronises."""
+    off = lib().vfr_bilstm_debug_offset(B, T, E, H, vocab)
+    f, r = workspace[off:off + 8].view(torch.int32).cpu().tolist()
+    return f, r
 
 
 def moment_offsets(clip_off: torch.Tensor) -> torch.Tensor:

@@ -1042,7 +1042,8 @@ struct LstmWs {
     unsigned *sync;                       // multi-step kernel: tickets, error word, completion counters (lstm_steps_sync_words)
     int64_t *tok_ext;
     int *len, *row_of, *xrow, *mcount, *hist;
-    size_t total;
+    unsigned *blocks;                     // DEBUG (option lstm_live_blocks bit 1): MFMA blocks issued by the fused steps, [direction]
+    size_t total, blocks_off;
 };
 static LstmWs carve(void *base, int64_t B, int T, int E, int H, int vocab)
 {
@@ -1074,6 +1075,8 @@ static LstmWs carve(void *base, int64_t B, int T, int E, int H, int vocab)
     }
     if (B <= 4) w.wt = take((size_t)2 * (E + H) * 4 * H);       // k-major weights of the vector-chain step (a few queries)
     if (B <= 64) w.hg = reinterpret_cast<unsigned long long *>(take_b(16 + (size_t)4 * B * H * sizeof(unsigned long long)));
+    w.blocks_off = off;
+    w.blocks = reinterpret_cast<unsigned *>(take_b(2 * sizeof(unsigned)));
     w.total = off;
     return w;
 }
@@ -1088,6 +1091,20 @@ size_t vfr_bilstm_workspace_bytes(int64_t B, int T, int E, int H, int vocab)
     return vfr::carve(nullptr, B, T, E, H, vocab).total;
 }
 
+int vfr_lstm_plan(int64_t rows, int H, int T, int cus, int *one_launch, int *tile, int64_t *slots)
+{
+    VFR_REQUIRE(rows > 0 && H > 0 && T > 0 && cus >= 0 && one_launch && tile && slots, VFR_EINVAL, "vfr_lstm_plan: bad argument");
+    const vfr::LstmPlan p = vfr::lstm_plan(rows, H, T, cus);
+    *one_launch = p.one_launch ? 1 : 0; *tile = p.tile; *slots = p.slots;
+    return VFR_OK;
+}
+
+size_t vfr_bilstm_debug_offset(int64_t B, int T, int E, int H, int vocab)
+{
+    if (B < 0 || T < 0 || E < 0 || H < 0) return 0;
+    return vfr::carve(nullptr, B, T, E, H, vocab).blocks_off;
+}
+
 int vfr_bilstm_final_f32(const int64_t *tokens, int64_t B, int T, const float *emb, int vocab, const float *len_tab,
                          const float *Wih_f, const float *Whh_f, const float *bih_f, const float *bhh_f,
                          const float *Wih_b, const float *Whh_b, const float *bih_b, const float *bhh_b, int E,
@@ -1097,6 +1114,7 @@ int vfr_bilstm_final_f32(const int64_t *tokens, int64_t B, int T, const float *e
     VFR_REQUIRE(tokens && emb && Wih_f && Whh_f && bih_f && bhh_f && Wih_b && Whh_b && bih_b && bhh_b && Wfc && bfc &&
                     out && B >= 0 && T > 0 && E > 0 && H > 0 && D > 0 && vocab > 0,
                 VFR_EINVAL, "vfr_bilstm_final_f32: bad argument");
+    vfr::note_lstm_multi_taken(0);                          // (every path but the one-launch tile kernel's)
     if (B == 0) return VFR_OK;
     VFR_REQUIRE(workspace && workspace_bytes >= vfr_bilstm_workspace_bytes(B, T, E, H, vocab), VFR_EWORKSPACE,
                 "vfr_bilstm_final_f32: workspace %zu < %zu bytes", workspace_bytes,
@@ -1217,12 +1235,13 @@ int vfr_bilstm_final_f32(const int64_t *tokens, int64_t B, int T, const float *e
     const int64_t R = B + 1;                                // GEMM rows: row 0 = all-pad query, then queries by length
     // tokens + one all-pad query -> embeddings of R queries
     {
-        const vfr::FillJob jobs[5] = {{w.tok_ext, tokens, (size_t)B * T * sizeof(int64_t), 0u},
+        const vfr::FillJob jobs[6] = {{w.tok_ext, tokens, (size_t)B * T * sizeof(int64_t), 0u},
                                       {w.tok_ext + (size_t)B * T, nullptr, (size_t)T * sizeof(int64_t), 0u},
                                       {w.c, nullptr, (size_t)2 * R * H * sizeof(float), 0u},
                                       {w.hcat, nullptr, (size_t)R * 2 * H * sizeof(float), 0u},
+                                      {w.blocks, nullptr, 2 * sizeof(unsigned), 0u},
                                       {w.sync, nullptr, w.sync ? vfr::lstm_steps_sync_words(R, T) * sizeof(unsigned) : 0, 0u}};
-        if (int rc = vfr::fill_regions(jobs, w.sync ? 5 : 4, st)) return rc;        // one launch instead of a copy and three memsets
+        if (int rc = vfr::fill_regions(jobs, w.sync ? 6 : 5, st)) return rc;        // one launch instead of a copy and three memsets
     }
     const bool fused = vfr::opt_gemm() != 0 && (E % 4) == 0 && (H % 4) == 0 &&
                        ((((uintptr_t)Wih_f) | ((uintptr_t)Whh_f) | ((uintptr_t)Wih_b) | ((uintptr_t)Whh_b)) & 15) == 0;
@@ -1259,7 +1278,12 @@ int vfr_bilstm_final_f32(const int64_t *tokens, int64_t B, int T, const float *e
                            vocab, w.tokidx);
         VFR_CHECK_LAUNCH("token_index_kernel");
     }
-    if (fused && table && w.sync && H <= 1024 && vfr::lstm_steps_supported(R, H)) {
+    unsigned *const blocks = (vfr::opt_lstm_live_blocks() & 2) ? w.blocks : nullptr;
+    // (the one-launch form needs its whole grid resident at once -- lstm_steps_resident; when it is not, the per-step launches)
+    const bool selected = fused && table && w.sync && vfr::lstm_steps_supported(R, H);
+    const bool one_launch = selected && vfr::lstm_steps_resident(R, H, T);
+    vfr::note_lstm_multi_taken(one_launch ? 1 : selected ? 2 : 0);
+    if (one_launch) {
         // ALL T steps of both directions in one launch (gemm.hip: lstm_steps_mfma_kernel): no partial round of workgroups at
         // the end of every step, no launch gap between steps.  Three rotating state buffers (the third pair lives in the
         // generic path's gates array, unused here); the final state is in buffer T % 3.
@@ -1269,7 +1293,7 @@ int vfr_bilstm_final_f32(const int64_t *tokens, int64_t B, int T, const float *e
             g[d].A2 = hbuf[0] + (size_t)d * H; g[d].lda2 = 2 * H; g[d].W2 = Whh[d]; g[d].ldw2 = H; g[d].K2 = H;
             g[d].bias = bih[d]; g[d].bias2 = bhh[d]; g[d].M = R; g[d].N = G;
             g[d].lstm_ldh = 2 * H; g[d].lstm_H = H; g[d].site = vfr::SITE_GEMM_LSTM_REC;
-            g[d].lstm_xrow = nullptr; g[d].lstm_mcount = d ? w.mcount : nullptr;
+            g[d].lstm_xrow = nullptr; g[d].lstm_mcount = d ? w.mcount : nullptr; g[d].lstm_blocks = blocks ? blocks + d : nullptr;
             g[d].Cin = w.ptab + (size_t)d * vocab * NP; g[d].ldc = NP;
         }
         if (int rc = vfr::lstm_steps_run(g[0], g[1], hbuf, cbuf, w.tokidx, w.mcount, w.sync, T, st)) return rc;
@@ -1297,6 +1321,7 @@ int vfr_bilstm_final_f32(const int64_t *tokens, int64_t B, int T, const float *e
                 g[d].lstm_h = hout + (size_t)d * H; g[d].lstm_ldh = 2 * H;
                 g[d].lstm_H = H; g[d].out = hout; g[d].site = vfr::SITE_GEMM_LSTM_REC;
                 g[d].lstm_xrow = w.xrow; g[d].lstm_mcount = d ? w.mcount : nullptr; g[d].lstm_step = step;
+                g[d].lstm_blocks = blocks ? blocks + d : nullptr;
                 if (table) {
                     g[d].A = g[d].A2; g[d].W = g[d].W2; g[d].lda = g[d].lda2; g[d].ldw = g[d].ldw2; g[d].K = 0;   // no x segment
                     g[d].Cin = w.ptab + (size_t)d * vocab * NP; g[d].ldc = NP;

@@ -9,6 +9,7 @@
 // Used by: visual MLP (model/models.py:21-26), BiLSTM input/recurrent projections and lang_fc
 // (model/models.py:40-47), BERT-branch Linear (:31), VGG fc6/fc7 (get_rgb_features.py:126).
 #include "vfr_common.h"
+#include <atomic>
 #include <type_traits>
 #include <vector>
 #include <cstdlib>
@@ -253,11 +254,29 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
     constexpr int TI = MI ? 2 * MI : 1;
     const int l15 = lane & 15, lq = lane >> 4;
     f32x4 acc[TI][4];
-    auto init_acc = [&]() {
+    // Fused LSTM step (inference forms, pipelined loop): TL = this wave's LIVE 16-row blocks -- those that hold at least one
+    // row below the direction's active count; none when the wave's 16-unit column half lies wholly past H.  The outputs of
+    // the other blocks are never stored, so nothing is issued for them: the tile is dispatched ONCE, below, to a K-loop
+    // instantiated for TL blocks (straight-line code like the full one; a full wave takes the TL == TI instantiation).  The
+    // count is wave-uniform and pinned to an SGPR (it derives from the wave index, a vector value).  A dead wave (TL == 0)
+    // keeps its share of the staging loads / stores and every barrier.  GemmArgs::lstm_live bit 0 switches it on.
+    constexpr std::integral_constant<int, TI> TIC{};
+    constexpr bool LIVE = LSTM && !PP && !TRAIN && NBUF == 2 && VFR_GEMM_PIPE;
+    int tl = TI;
+    if constexpr (LIVE) {
+        if (g.lstm_live & 1) {
+            const int64_t left = Mrows - m0 - wm * (16 * TI);
+            int n = left >= 16 * TI ? TI : left > 0 ? (int)((left + 15) >> 4) : 0;
+            if (by * 32 + wn * 16 >= g.lstm_H) n = 0;
+            tl = __builtin_amdgcn_readfirstlane(n);
+        }
+    }
+    auto init_acc = [&](auto tlc) {
+        constexpr int TL = decltype(tlc)::value;         // blocks to initialise: the first TL of the wave's TI
 #ifdef VFR_LSTM_NOGATHER      /* TIMING EXPERIMENT ONLY (wrong results): accumulators start from zero, no table gather */
         if (LSTM && g.lstm_tok) {
 #pragma unroll
-            for (int ti = 0; ti < TI; ++ti)
+            for (int ti = 0; ti < TL; ++ti)
 #pragma unroll
                 for (int tj = 0; tj < 4; ++tj) acc[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
             return;
@@ -266,9 +285,9 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         if (LSTM && g.lstm_tok) {
             // chains start from the vocabulary input-projection table: P[lstm_tok[row]][tile column].  Two batched load
             // rounds (all table-row indices, then all accumulators), not dependent pairs one after the other.
-            int64_t prow[TI][4];
+            int64_t prow[TL ? TL : 1][4];
     #pragma unroll
-            for (int ti = 0; ti < TI; ++ti)
+            for (int ti = 0; ti < TL; ++ti)
     #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int64_t row = m0 + wm * (16 * TI) + ti * 16 + 4 * lq + r;
@@ -276,14 +295,14 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
                 }
             const float *pcol = g.Cin + (int64_t)by * MBN + wn * 64 + l15;
     #pragma unroll
-            for (int ti = 0; ti < TI; ++ti)
+            for (int ti = 0; ti < TL; ++ti)
     #pragma unroll
                 for (int r = 0; r < 4; ++r)
     #pragma unroll
                     for (int tj = 0; tj < 4; ++tj) acc[ti][tj][r] = pcol[prow[ti][r] * g.ldc + tj * 16];
         } else {
     #pragma unroll
-            for (int ti = 0; ti < TI; ++ti)
+            for (int ti = 0; ti < TL; ++ti)
     #pragma unroll
                 for (int tj = 0; tj < 4; ++tj)
     #pragma unroll
@@ -590,13 +609,14 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
             tfb[1][tj] = ktail > 4 ? pw[4] : 0.0f;
         }
     }
-    auto tail_mfma = [&]() {
+    auto tail_mfma = [&](auto tlc) {
+        constexpr int TL = decltype(tlc)::value;         // live row blocks
         if (LSTM && ktail) {
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 if (s == 1 && ktail <= 4) break;
 #pragma unroll
-                for (int ti = 0; ti < TI_; ++ti)
+                for (int ti = 0; ti < TL; ++ti)
 #pragma unroll
                     for (int tj = 0; tj < 4; ++tj)
                         acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(tfa[s][ti], tfb[s][tj], acc[ti][tj], 0, 0, 0);
@@ -695,14 +715,15 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
     constexpr int TIc = MI ? 2 * MI : 1;
     float cprev[LSTM ? TIc : 1][4];
     float bi = 0.f, bf = 0.f, bg = 0.f, bo = 0.f;
-    auto load_cell_inputs = [&]() {
-        if constexpr (LSTM) {
+    auto load_cell_inputs = [&](auto tlc) {
+        constexpr int TL = decltype(tlc)::value;         // live row blocks (none: no cell of this wave is stored, nothing to fetch)
+        if constexpr (LSTM && TL > 0) {
             const int H = g.lstm_H, unit = by * 32 + wn * 16 + (lane & 15);
             const int uc = unit < H ? unit : H - 1;
             bi = g.bias[uc] + g.bias2[uc]; bf = g.bias[H + uc] + g.bias2[H + uc];
             bg = g.bias[2 * H + uc] + g.bias2[2 * H + uc]; bo = g.bias[3 * H + uc] + g.bias2[3 * H + uc];
 #pragma unroll
-            for (int ti = 0; ti < TIc; ++ti)
+            for (int ti = 0; ti < TL; ++ti)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int64_t row = m0 + wm * (16 * TIc) + ti * 16 + 4 * (lane >> 4) + r;
@@ -714,11 +735,28 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
     };
     constexpr bool CELL_EARLY = LSTM && !PP && NBUF == 2 && VFR_GEMM_PIPE && VFR_LSTM_CELL_EARLY;
     auto gload_main = [&](int k0, auto sc) { if (LSTM) gload_seg(k0, sc); else if (CFAST) gload_conv_fast(k0, sc); else if (CONV) gload_conv(k0, sc); else gload_full(k0, sc); };
+    // Fused LSTM step, dispatched form: the gate epilogue of the wave's first TL row blocks (the live ones)
+    auto lstm_epilogue = [&](auto TLC) {
+        constexpr int TL = decltype(TLC)::value;
+        // (gemm_lstm_epilogue.inc takes from this scope: TL, TLC; TI, TRAIN, MULTI, CELL_EARLY; g, by, m0, Mrows, wm, wn, l15, lq,
+        // acc, cprev, bi, bf, bg, bo, load_cell_inputs -- and declares H, unit, valid, cnew, hnew, gsave)
+        if constexpr (LSTM && TL > 0) {
+#include "gemm_lstm_epilogue.inc"
+        }
+        GSTAMP(2)
+#ifdef VFR_GEMM_STAMPS
+        if (lane == 0) for (int i = 0; i < 3; ++i) atomicAdd(&g_gemm_stamps[i], gst[i]);
+        if (tid == 0) atomicAdd(&g_gemm_stamps[3], 1ull);
+#endif
+        // DEBUG (GemmArgs::lstm_blocks, null in normal use): count the (16-row, 16-unit) blocks this wave issued MFMAs for.
+        // The counter is read by tests only; no output is computed from it.
+        if constexpr (LIVE) { if (g.lstm_blocks && lane == 0 && TL > 0) atomicAdd(g.lstm_blocks, (unsigned)TL); }
+    };
     if (PP) {
         // group g runs  C0 L1 C1 L2 ... C(nk-1)  delayed by g phases;  Ck = MFMA block on K-tile k (LDS), Lk = K-tile k from
         // registers to LDS + issue the loads of K-tile k+1.  One workgroup barrier per phase.
         const int nk = nk_full;
-        init_acc();
+        init_acc(TIC);
         if (active && nk > 0) { gload_main(0, S0); swrite(0, S0); if (nk > 1) gload_main(MBK, S0); }
         __syncthreads();
         GSTAMP(0)
@@ -742,103 +780,33 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         // so the LDS writes, the load issue and the first fragment reads of the next tile all run under MFMAs of this one.
         constexpr int DEPTH = LSTM ? VFR_LSTM_DEPTH : 2, RING = DEPTH == 1 ? 2 : 4, NS = MBK / 4;
         const int nk = nk_full;
-        float fa[RING][TI], fb[RING][4];
-        auto frag_read = [&](int buf, int slice, int slot) {
-            const float *As = lds + buf * BUF_FLOATS, *Ws = As + A_FLOATS;
-            const float *ap = &As[lds_off(wm * (16 * TI) + l15, lq) + slice * 4];
-            const float *wp = &Ws[lds_off(wn * 64 + l15, lq) + slice * 4];
-#pragma unroll
-            for (int ti = 0; ti < TI; ++ti) fa[slot][ti] = ap[ti * RBLK];
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj) fb[slot][tj] = wp[tj * RBLK];
-        };
-        // the first K-tile's loads are in flight while the accumulators are initialised (C-in / the LSTM table gather: two
-        // dependent load rounds whose latency would otherwise stand alone at the head of every tile)
-        if (nk > 0) gload_main(0, S0);
-        init_acc();
-        if constexpr (CELL_EARLY) load_cell_inputs();
-        // Accumulators that start from LOADED values (C-in, the LSTM projection-table gather) must have landed before the loop is
-        // entered: otherwise the waitcnt pass, merging the loop-entry state into the loop header, guards the first MFMAs of EVERY
-        // trip with vmcnt(3) .. vmcnt(0) -- which on the back edge drains the staging loads requested five slices earlier, i.e. the
-        // prefetch is thrown away every second K-tile (seen in the ISA of lstm_step_mfma_pair).  The values are needed by the
-        // first MFMA anyway; waiting here, before K-tile 1 is requested, costs nothing.
-        // (unconditional: behind a run-time test the wait would itself sit on one arm of a join)
-        __builtin_amdgcn_s_waitcnt(0x0F70);                                                    // vmcnt(0)
-        if (nk > 0) {
-            swrite(0, S0);
-            if constexpr (DEEP) {        // K-tile 1 into set 1, K-tile 2 into set 0 (free again): two tiles in flight from here on
-                gload_main((nk > 1 ? 1 : 0) * MBK, S1);
-                gload_main((nk > 2 ? 2 : nk - 1) * MBK, S0);
-            } else {
-                gload_main((nk > 1 ? 1 : 0) * MBK, S0);
+        // TL = row blocks of this wave that are computed: TI, or the live count of an LSTM tile's wave (see LIVE above).  With
+        // TL == 0 the wave only stages: its loads, its LDS stores (as one block at slice 1) and the barriers.
+        if constexpr (LIVE) {
+            // (gemm_pipe_loop.inc takes from this scope: TL, TLC; TI, NA, NW, RBLK, BUF_FLOATS, A_FLOATS, DEPTH, RING, NS, DEEP,
+            // CELL_EARLY, the kernel's template flags; nk, lds, lds_off, wm, wn, l15, lq, acc; S0, S1; gload_main, swrite,
+            // swrite_piece, init_acc, load_cell_inputs -- and declares fa, fb, frag_read, ktile, kt)
+            auto pipe = [&](auto TLC) {
+                constexpr int TL = decltype(TLC)::value;
+#include "gemm_pipe_loop.inc"
+            };
+            // one dispatch per tile on the wave's live count (an SGPR); each arm is the whole step for that many row blocks.  A
+            // full wave falls through to the in-place copy below: the code (and the register count) of the step as it was.
+            auto step = [&](auto tlc) { pipe(tlc); tail_mfma(tlc); GSTAMP(1) lstm_epilogue(tlc); };
+            if (tl != TI) {
+                if (tl == 0) step(std::integral_constant<int, 0>{});
+                else if constexpr (TI == 2) step(std::integral_constant<int, 1>{});
+                else if constexpr (TI == 4) {
+                    if (tl == 1) step(std::integral_constant<int, 1>{});
+                    else if (tl == 2) step(std::integral_constant<int, 2>{});
+                    else step(std::integral_constant<int, 3>{});
+                }
+                return;
             }
         }
-        __syncthreads();
-        GSTAMP(0)
-        if (nk > 0) {
-#pragma unroll
-            for (int d = 0; d < DEPTH; ++d) frag_read(0, d, d % RING);
-        }
-        // two K-tiles per trip, so the LDS buffer of every read and write is a compile-time constant and folds into the
-        // instruction's immediate offset (a run-time buffer index cost 10-15 vector adds per K-tile)
-        auto ktile = [&](int kt, auto cbc) {
-            constexpr int cb = decltype(cbc)::value, nb = cb ^ 1;
-#pragma unroll
-            for (int k4 = 0; k4 < NS; ++k4) {
-                const int sn = k4 + DEPTH;                   // slice whose fragments are fetched now
-#ifndef VFR_GEMM_NOSYNC
-                if (sn == NS) __syncthreads();               // K-tile kt+1 (written at slice 1) is visible from here on
-#endif
-                if (sn < NS) frag_read(cb, sn, sn % RING);
-                else         frag_read(nb, sn - NS, sn % RING);    // (past the last K-tile: stale data, never used)
-                __builtin_amdgcn_sched_barrier(0);
-                // VFR_GEMM_SPREAD: the staging stores of K-tile kt + 1 go out ONE behind each MFMA of slices 1 and 2 instead of as a
-                // block behind slice 1 (a wave alone on its SIMD issues no MFMA while it moves 5-8 float4 to the LDS: 254 cycles
-                // per K-tile of a 32-row tile)
-                constexpr int NM = TI * 4, NPIECE = NA + NW;
-                static_assert(!VFR_GEMM_SPREAD || NPIECE <= 2 * NM, "staging pieces must fit behind the MFMAs of two slices");
-#pragma unroll
-                for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < 4; ++tj) {
-                        acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[k4 % RING][ti], fb[k4 % RING][tj], acc[ti][tj], 0, 0, 0);
-                        if (VFR_GEMM_SPREAD && (k4 == 1 || k4 == 2)) {
-                            const int piece = (k4 - 1) * NM + ti * 4 + tj;
-                            if (piece < NPIECE) swrite_piece(nb, std::integral_constant<int, DEEP ? nb : 0>{}, piece);
-                        }
-                    }
-#if VFR_GEMM_SPREAD == 2
-                // (pin the order: MFMA, [the piece's zero-selects], its LDS store -- left alone the scheduler hangs four of the stores
-                // behind the first MFMA)
-                if (k4 == 1 || k4 == 2) {
-#pragma unroll
-                    for (int m = 0; m < NM; ++m) {
-                        const int piece = (k4 - 1) * NM + m;
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        if (piece < NPIECE) {
-                            if (((CONV && !CHALO) || (LSTM && !LFAST)) && piece < NA) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                        }
-                    }
-                }
-#endif
-                __builtin_amdgcn_sched_barrier(0);
-                // DEEP: K-tile kt + 1 sits in register set nb (= its parity); once it is in LDS that set takes K-tile kt + 3,
-                // while set cb still holds K-tile kt + 2 in flight
-                if (!VFR_GEMM_SPREAD && k4 == 1) swrite(nb, std::integral_constant<int, DEEP ? nb : 0>{});
-                if (k4 == VFR_GLOAD_SLICE) {
-                    const int ahead = DEEP ? 3 : 2;
-                    const int t2 = kt + ahead < nk ? kt + ahead : nk - 1;
-                    gload_main(t2 * MBK, std::integral_constant<int, DEEP ? nb : 0>{});
-                }
-            }
-        };
-        int kt = 0;
-        for (; kt + 1 < nk; kt += 2) {
-            ktile(kt, std::integral_constant<int, 0>{});
-            ktile(kt + 1, std::integral_constant<int, 1>{});
-        }
-        if (kt < nk) ktile(kt, std::integral_constant<int, 0>{});
+        constexpr int TL = TI;
+        constexpr std::integral_constant<int, TL> TLC{};
+#include "gemm_pipe_loop.inc"
         if (!CONV && !LSTM && (g.K % MBK)) {   // partial last tile: guarded loads, zero padded (fma(0,0,acc) == acc)
             __syncthreads();
             gload_tail(nk_full * MBK, S0);
@@ -847,7 +815,7 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
             compute(0);
         }
     } else {
-    init_acc();
+    init_acc(TIC);
     if (nk_full > 0) { gload_main(0, S0); swrite(0, S0); }
     __syncthreads();
     GSTAMP(0)
@@ -875,58 +843,19 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
     }
     }
     if (PP && !active) return;
-    tail_mfma();
+    tail_mfma(TIC);
 
     GSTAMP(1)
     if (LSTM) {
-        // tile columns are (gate, unit): a lane holds i, f, g, o of unit 32*blockIdx.y + 16*wn + (lane & 15) in its four column
-        // tiles, for 4*TI rows -- every cell is finished by ONE lane, no exchange
-        const int H = g.lstm_H, unit = by * 32 + wn * 16 + l15;
-        const bool valid = unit < H;
-        const int uc = valid ? unit : H - 1;
-        if constexpr (!CELL_EARLY) load_cell_inputs();
-        // batched and branch-free: the previous-cell loads first (clamped addresses), then 4*TI independent gate evaluations
-        // in ONE basic block (the asm pins the results ahead of the predicated stores; hipcc otherwise sinks each cell's ~190
-        // instructions into its own store predicate, one serial dependency chain after the other)
-        float cnew[TI][4], hnew[TI][4];
-        float gsave[TRAIN ? TI : 1][4][4];
-#pragma unroll
-        for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float ig = c_sigmoidf(acc[ti][0][r] + bi);
-                const float fg = c_sigmoidf(acc[ti][1][r] + bf);
-                const float gg = c_tanhf(acc[ti][2][r] + bg);
-                const float og = c_sigmoidf(acc[ti][3][r] + bo);
-                cnew[ti][r] = __builtin_fmaf(fg, cprev[ti][r], ig * gg);
-                hnew[ti][r] = og * c_tanhf(cnew[ti][r]);
-                asm volatile("" : "+v"(cnew[ti][r]), "+v"(hnew[ti][r]));
-                if constexpr (TRAIN) { gsave[ti][r][0] = ig; gsave[ti][r][1] = fg; gsave[ti][r][2] = gg; gsave[ti][r][3] = og; }
-            }
-#pragma unroll
-        for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t row = m0 + wm * (16 * TI) + ti * 16 + 4 * lq + r;
-                if (valid && row < Mrows) {
-                    if constexpr (MULTI) {
-                        __hip_atomic_store(g.lstm_c + row * H + unit, cnew[ti][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(g.lstm_h + row * g.lstm_ldh + unit, hnew[ti][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    } else {
-                    g.lstm_c[row * H + unit] = cnew[ti][r];
-                    g.lstm_h[row * g.lstm_ldh + unit] = hnew[ti][r];
-                    }
-                    if constexpr (TRAIN) {
-                        float *g4 = g.lstm_gates + row * 4 * H + unit;
-                        g4[0] = gsave[ti][r][0]; g4[H] = gsave[ti][r][1]; g4[2 * H] = gsave[ti][r][2]; g4[3 * H] = gsave[ti][r][3];
-                    }
-                }
-            }
+        constexpr int TL = TI;
+        constexpr std::integral_constant<int, TL> TLC{};
+#include "gemm_lstm_epilogue.inc"
         GSTAMP(2)
 #ifdef VFR_GEMM_STAMPS
         if (lane == 0) for (int i = 0; i < 3; ++i) atomicAdd(&g_gemm_stamps[i], gst[i]);
         if (tid == 0) atomicAdd(&g_gemm_stamps[3], 1ull);
 #endif
+        if constexpr (LIVE) { if (g.lstm_blocks && lane == 0) atomicAdd(g.lstm_blocks, (unsigned)TI); }     // DEBUG, see lstm_epilogue
         return;
     }
     if (CONV && (g.epi & EPI_POOL2)) {
@@ -1069,12 +998,15 @@ __global__ __launch_bounds__(256, MI <= 1 ? 3 : VFR_LSTM_WAVES) void lstm_step_m
 // reverse direction, for row tile 0 (the shared all-pad row); it waits until the completion counters of those row tiles
 // read `ncol`.  The state rotates through THREE buffers (step s reads s % 3, writes (s + 1) % 3), and a task also waits for
 // ALL of step s - 2 (whose reads are the last users of the buffer it writes).
-// No deadlock, whatever is resident: every dependency points to an earlier step, every group's list is sorted by step, and
-// a ticket is only ever held by a workgroup that is running -- so the earliest unfinished task of the whole launch is always
-// either running or next in line for a running workgroup.  (Nothing here needs the grid to be co-resident: unlike the
-// register-resident sequence kernels a workgroup never waits for one that has not started.)  The waits are bounded all
-// the same (a bug or a lost workgroup must not hang the device): on expiry the error word is raised, every workgroup leaves,
-// and the rescue kernel behind the launch (bilstm.hip) re-encodes the batch.
+// No deadlock INSIDE a group: every dependency points to an earlier step, every group's list is sorted by step, and a ticket
+// is only ever held by a workgroup that is running -- so the earliest unfinished task of a group is always either running or
+// next in line for a running workgroup of that group.  ACROSS groups that is not enough: a row tile is complete when the
+// column tiles of all eight groups are, and a group's tickets are drawn only by workgroups with blockIdx & 7 == group -- were
+// one group's workgroups not resident, the others would spin on its counters and keep their slots.  So the grid must be
+// co-resident: lstm_steps_resident() checks at launch that it fits (occupancy of this kernel x CUs) and the caller takes the
+// per-step launches when it does not.  That covers this process's own launch, not another process on the device: the waits
+// are bounded all the same (nor must a bug or a lost workgroup hang the device): on expiry the error word is raised, every
+// workgroup leaves, and the rescue kernel behind the launch (bilstm.hip) re-encodes the batch.
 // Coherence: the producer of a row's h ran on another XCD, whose L2 this one does not snoop -- see MULTI in the kernel body.
 struct LstmSteps {
     GemmArgs p[2];                 // step-invariant arguments per direction (W2 / ldw2 / biases / Cin = the projection table / M = rows ...)
@@ -1338,10 +1270,11 @@ int lstm_step_pair(const GemmArgs &g0, const GemmArgs &g1, hipStream_t st)
     // rows (a rank's share of the batch on 8 GPUs) the step is hardly more than one round and 32-row tiles at three
     // workgroups per CU balance the CUs better still (tools/lstm_tile_sweep.py: -1 % at 625 rows, -11 % at 313; alone the
     // encoder also gains 1-2 % at 1250 / 2500 rows, but beside the clip encoder on the other stream it does not; +5 % at 5000).
-    const int tile = opt_lstm_tile() ? opt_lstm_tile() : (g0.M <= 700 ? 3 : 1);
+    const int tile = opt_lstm_tile() ? opt_lstm_tile() : (g0.M <= 700 ? 3 : 1);       // (= lstm_plan's tile for the per-step form)
     const int ncol = (int)cdiv(g0.lstm_H, 32), cpx = (int)cdiv(ncol, 8);
     const bool xcd = opt_lstm_xcd() && !(tile == 2 && opt_gemm_pp());
     if (xcd) gp.p[0].xcd_cols = gp.p[1].xcd_cols = cpx;
+    gp.p[0].lstm_live = gp.p[1].lstm_live = opt_lstm_live_blocks() & 1;
     auto grid_for = [&](int rows) {
         const unsigned rt = (unsigned)cdiv(g0.M, rows);
         return xcd ? dim3(rt * (unsigned)cpx * 8u, 1, 2) : dim3(rt, (unsigned)ncol, 2);
@@ -1383,16 +1316,59 @@ int lstm_step_pair(const GemmArgs &g0, const GemmArgs &g1, hipStream_t st)
     return VFR_OK;
 }
 
-// all T steps in one launch (lstm_steps_mfma_kernel); g0 / g1 carry the step-invariant arguments of the two directions
-bool lstm_steps_supported(int64_t R, int H)
+// Which form the fused steps of a batch of R GEMM rows (queries + 1), hidden size H, T steps take on a device of `cus` CUs -- a
+// pure function of its arguments and the options (no device call: tests/test_lstm_live_blocks_host.py pins it through
+// vfr_lstm_plan).  one_launch: lstm_steps_mfma_kernel is SELECTED (the caller still needs the projection table and the
+// residency check, lstm_steps_resident); tile: lstm_tile numbering (1 = 64 rows, 2 = 128, 3 = 32) of the form taken; slots: the
+// one-launch kernel's grid, 0 for the per-step launches.
+//   lstm_multi 1: one launch wherever the shape is supported, tile height as the per-step launch picks it.
+//   lstm_multi 2 (default): one launch with 128-row tiles from lstm_multi_min rows on, where every XCD group has column tiles
+//   (H >= 512: measured at H = 1000 only) and no tile height is forced (lstm_tile is a cross-check of the per-step launch).
+//   The cross-check switches of the per-step launch -- general K-loop, first step with its recurrent part, launch order --
+//   select the per-step path.
+LstmPlan lstm_plan(int64_t R, int H, int T, int cus)
 {
-    const int rem = H % MBK;
-    // (the cross-check switches of the per-step launch -- general K-loop, first step with its recurrent part, launch order, 128-row
-    // tiles -- select the per-step path)
-    return opt_lstm_multi() && opt_lstm_fast() && opt_lstm_skip0() && opt_lstm_xcd() && bool(VFR_GEMM_PIPE) && VFR_LSTM_NBUF == 2 && (H % 4) == 0 && H >= MBK && (rem == 0 || (H > MBK && rem <= 8)) &&
-           ((R + 1) * 2 * (int64_t)H + MBK) * 4 < (1ll << 32);
+    LstmPlan p{};
+    const int rem = H % MBK, multi = opt_lstm_multi(), forced = opt_lstm_tile();
+    const bool wanted = multi == 1 || (multi == 2 && forced == 0 && R >= opt_lstm_multi_min() && H >= 512);
+    p.one_launch = wanted && opt_lstm_fast() && opt_lstm_skip0() && opt_lstm_xcd() && bool(VFR_GEMM_PIPE) && VFR_LSTM_NBUF == 2 &&
+                   (H % 4) == 0 && H >= MBK && H <= 1024 && (rem == 0 || (H > MBK && rem <= 8)) && ((R + 1) * 2 * (int64_t)H + MBK) * 4 < (1ll << 32);
+    p.tile = forced ? forced : (R <= 700 ? 3 : 1);               // 32-row tiles for small batches (lstm_step_pair)
+    if (p.one_launch) {
+        if (multi == 2) p.tile = 2;
+        else if (p.tile != 2 && p.tile != 3) p.tile = 1;
+        const int64_t rows = p.tile == 3 ? 32 : p.tile == 2 ? 128 : 64;
+        const int64_t per_step_max = 2 * cdiv(R, rows) * cdiv(cdiv(H, 32), 8) * 8;
+        p.slots = (int64_t)cus * (p.tile == 2 ? 2 : 3) / 8 * 8;          // workgroups per CU the kernels are built for, whole groups of 8
+        if (p.slots > per_step_max * T) p.slots = per_step_max * T;
+        if (p.slots < 8) p.slots = 8;
+    }
+    return p;
 }
+// all T steps in one launch (lstm_steps_mfma_kernel); g0 / g1 carry the step-invariant arguments of the two directions
+bool lstm_steps_supported(int64_t R, int H) { return lstm_plan(R, H, 1, 0).one_launch; }
 size_t lstm_steps_sync_words(int64_t R, int T) { return 16 + (size_t)T + (size_t)T * 2 * (size_t)cdiv(R, 32); }
+// The one-launch kernel's groups wait for each other (see above): its whole grid must be resident at once.  Asked of the
+// runtime per device and tile form, once: workgroups of this kernel a CU holds x CUs >= the grid.  A host-side check only.
+bool lstm_steps_resident(int64_t R, int H, int T)
+{
+    static std::atomic<int> per_cu[VFR_MAX_DEVICES][3];               // 0: not asked yet, -1: the query failed
+    const LstmPlan plan = lstm_plan(R, H, T, device_cu_count());
+    if (!plan.one_launch) return false;
+    const int tile = plan.tile;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const bool cached = dev >= 0 && dev < VFR_MAX_DEVICES;
+    int n = cached ? per_cu[dev][tile - 1].load() : 0;
+    if (n == 0) {
+        const hipError_t e = tile == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lstm_steps_mfma_kernel<0>, 256, 0)
+                           : tile == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lstm_steps_mfma_kernel<2>, 256, 0)
+                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lstm_steps_mfma_kernel<1>, 256, 0);
+        if (e != hipSuccess || n <= 0) { (void)hipGetLastError(); n = -1; }
+        if (cached) per_cu[dev][tile - 1].store(n);
+    }
+    return n > 0 && (int64_t)n * device_cu_count() >= plan.slots;
+}
 int lstm_steps_run(const GemmArgs &g0, const GemmArgs &g1, float *const hbuf[3], float *const cbuf[3], const int *tokidx, const int *mcount,
                    unsigned *sync, int T, hipStream_t st)
 {
@@ -1403,22 +1379,20 @@ int lstm_steps_run(const GemmArgs &g0, const GemmArgs &g1, float *const hbuf[3],
         VFR_REQUIRE(((g->lda2 | g->ldw2) & 3) == 0 && (((uintptr_t)g->W2) & 15) == 0 && (4ll * g->lstm_H * g->ldw2 + MBK) * 4 < (1ll << 32), VFR_EUNSUPPORTED,
                     "lstm_steps_run: operand strides must be multiples of 4 floats, 16-byte aligned, under 4 GB");
     }
-    ProfScope prof(g0.site, st);
+    ProfScope prof(g0.site, st, T);          // one launch doing the work of T launches of the site: counted as T
     LstmSteps a{};
     a.p[0] = g0; a.p[1] = g1;
-    for (int d = 0; d < 2; ++d) { a.p[d].K = 0; a.p[d].W = a.p[d].W2; a.p[d].ldw = a.p[d].ldw2; a.p[d].lda = a.p[d].lda2; a.p[d].xcd_cols = 0; }
+    for (int d = 0; d < 2; ++d) { a.p[d].K = 0; a.p[d].W = a.p[d].W2; a.p[d].ldw = a.p[d].ldw2; a.p[d].lda = a.p[d].lda2; a.p[d].xcd_cols = 0; a.p[d].lstm_live = opt_lstm_live_blocks() & 1; }
     for (int i = 0; i < 3; ++i) { a.hbuf[i] = hbuf[i]; a.cbuf[i] = cbuf[i]; }
     a.tokidx = tokidx; a.mcount = mcount; a.sync = sync; a.T = T;
     a.ncol = (int)cdiv(g0.lstm_H, 32); a.cpx = (int)cdiv(a.ncol, 8);
-    const int tile = opt_lstm_tile() == 3 || (opt_lstm_tile() == 0 && g0.M <= 700) ? 3 : opt_lstm_tile() == 2 ? 2 : 1;      // 32-row tiles for small batches (as lstm_step_pair)
+    const LstmPlan plan = lstm_plan(g0.M, g0.lstm_H, T, device_cu_count());
+    const int tile = plan.tile;
     a.rt_max = (int)cdiv(g0.M, 32);
     a.fault_task = opt_lstm_persist_fault();
     a.max_spins = a.fault_task >= 0 ? 1u << 15 : 1u << 22;       // x (~1 us per poll): seconds -- only ever reached through a bug or a lost workgroup
-    const int64_t rows = tile == 3 ? 32 : tile == 2 ? 128 : 64;
-    const int64_t per_step_max = 2 * cdiv(g0.M, rows) * a.cpx * 8;
-    int64_t slots = (int64_t)device_cu_count() * (tile == 2 ? 2 : 3) / 8 * 8;
-    if (slots > per_step_max * T) slots = per_step_max * T;
-    if (slots < 8) slots = 8;
+    VFR_REQUIRE(lstm_steps_resident(g0.M, g0.lstm_H, T), VFR_EUNSUPPORTED, "lstm_steps_run: the grid is not resident at once on this device (use the per-step launches)");
+    const int64_t slots = plan.slots;
     if (tile == 3)      hipLaunchKernelGGL(lstm_steps_mfma_kernel<0>, dim3((unsigned)slots), dim3(256), 0, st, a);
     else if (tile == 2) hipLaunchKernelGGL(lstm_steps_mfma_kernel<2>, dim3((unsigned)slots), dim3(256), 0, st, a);
     else                hipLaunchKernelGGL(lstm_steps_mfma_kernel<1>, dim3((unsigned)slots), dim3(256), 0, st, a);

@@ -30,7 +30,10 @@ static std::atomic<int> g_opt_smallq_select{1};    // 1: the few-queries path ta
 static std::atomic<int> g_opt_lstm_persist_min{2}; // batches ABOVE this many queries (up to 32, the model's shape) take the single-launch MFMA sequence kernel; 32: never
 static std::atomic<int> g_opt_lstm_persist_fault{-1}; // TEST HOOK: workgroup of the single-launch sequence kernels that withholds its h of step 1 (-1: none)
 static std::atomic<int> g_opt_lstm_persist_max{32}; // ... and up to this many.  33 .. 64 are possible (two parts of <= 32 queries taking turns on the same resident weights): bit-identical, but 0.70 ms per 64-query pass against 0.62 for the tile steps (the two-part kernel's 275 weight registers + two parts' state spill): off by default
-static std::atomic<int> g_opt_lstm_multi{0};       // EXPERIMENT (off): 1 = all T steps of the fused BiLSTM in ONE launch (gemm.hip: lstm_steps_mfma_kernel; 128-row tiles with lstm_tile 2) -- same bits; measured no faster than one launch per step at 5 000 queries, 4-5 % faster around 2 500 (HISTORY.md)
+static std::atomic<int> g_opt_lstm_multi{2};       // all T steps of the fused BiLSTM in ONE launch (gemm.hip: lstm_steps_mfma_kernel) -- same bits as one launch per step.  2 (default): automatic -- from lstm_multi_min rows on, at H >= 512, with 128-row tiles (where it measured faster: HISTORY.md round 17; below ~2 000 rows the hand-overs between dependent tasks cost more than kernel boundaries) and only while lstm_tile is 0; 1: always (tile height by lstm_tile); 0: never
+static std::atomic<int> g_opt_lstm_multi_min{2500}; // lstm_multi 2: GEMM rows (queries + 1) from which the one-launch form is taken
+static std::atomic<int> g_opt_lstm_live_blocks{1}; // fused LSTM step, bit 0 (default on): a wave issues matrix work and gate epilogue only for its live 16-row blocks (rows below the active count, units below H) -- same bits; 0: every block of the tile (cross-check).  Bit 1 (tests): count the issued blocks in the workspace (vfr_bilstm_debug_offset)
+static std::atomic<int> g_opt_lstm_multi_taken{0}; // READ-ONLY (written by every vfr_bilstm_final_f32 call): 1 = that call ran its steps in the one-launch kernel; 2 = it was selected (option, shape) but its grid was not resident at once, so the per-step launches ran; 0 = any other path
 static std::atomic<int> g_opt_lstm_fast{1};        // 1: the table-start LSTM step without selects in its K-loop where the launch qualifies; 0: always the general form (cross-check)
 static std::atomic<int> g_opt_smallq_rank{8};       // N: few-queries path, video-selection form, from N queries on: rank counts with lane = video (smallq_rank_kernel); 0: always the moment kernel (cross-check)
 static std::atomic<int> g_opt_kth_seed{1};          // 1: stage A of the top-k threshold ladder takes its seed by bisection on the score bits (topk_kth_seed_kernel); 0: by the merge kernel (cross-check)
@@ -46,10 +49,10 @@ struct Opt { const char *name; std::atomic<int> *v; };
 static const Opt g_opts[] = {
     {"gemm", &g_opt_gemm}, {"profile", &g_opt_profile}, {"score_fast", &g_opt_score_fast}, {"score_split", &g_opt_score_split},
     {"score_pre_b", &g_opt_score_pre_b}, {"score_smallq", &g_opt_score_smallq}, {"score_tasks", &g_opt_score_tasks}, {"lstm_skip0", &g_opt_lstm_skip0},
-    {"lstm_xcd", &g_opt_lstm_xcd}, {"gemm_small", &g_opt_gemm_small}, {"lstm_tile", &g_opt_lstm_tile}, {"lstm_small4", &g_opt_lstm_small4}, {"lstm_persist", &g_opt_lstm_persist}, {"lstm_persist_min", &g_opt_lstm_persist_min}, {"lstm_fast", &g_opt_lstm_fast}, {"lstm_multi", &g_opt_lstm_multi}, {"lstm_persist_max", &g_opt_lstm_persist_max}, {"lstm_persist_fault", &g_opt_lstm_persist_fault}, {"vgg_fuse_pool", &g_opt_vgg_fuse_pool}, {"vgg_direct1", &g_opt_vgg_direct1}, {"vgg_halo", &g_opt_vgg_halo}, {"score_kth_seed", &g_opt_kth_seed}, {"score_smallq_rank", &g_opt_smallq_rank}, {"score_smallq_select", &g_opt_smallq_select}, {"gemm_pp", &g_opt_gemm_pp}, {"score_mfma_min", &g_opt_mfma_min}, {"lstm_small", &g_opt_lstm_small}, {"score_defer", &g_opt_score_defer}, {"score_sort", &g_opt_score_sort}, {"score_hist", &g_opt_score_hist}, {"score_i8", &g_opt_score_i8},
+    {"lstm_xcd", &g_opt_lstm_xcd}, {"gemm_small", &g_opt_gemm_small}, {"lstm_tile", &g_opt_lstm_tile}, {"lstm_small4", &g_opt_lstm_small4}, {"lstm_persist", &g_opt_lstm_persist}, {"lstm_persist_min", &g_opt_lstm_persist_min}, {"lstm_fast", &g_opt_lstm_fast}, {"lstm_multi", &g_opt_lstm_multi}, {"lstm_multi_min", &g_opt_lstm_multi_min}, {"lstm_multi_taken", &g_opt_lstm_multi_taken}, {"lstm_live_blocks", &g_opt_lstm_live_blocks}, {"lstm_persist_max", &g_opt_lstm_persist_max}, {"lstm_persist_fault", &g_opt_lstm_persist_fault}, {"vgg_fuse_pool", &g_opt_vgg_fuse_pool}, {"vgg_direct1", &g_opt_vgg_direct1}, {"vgg_halo", &g_opt_vgg_halo}, {"score_kth_seed", &g_opt_kth_seed}, {"score_smallq_rank", &g_opt_smallq_rank}, {"score_smallq_select", &g_opt_smallq_select}, {"gemm_pp", &g_opt_gemm_pp}, {"score_mfma_min", &g_opt_mfma_min}, {"lstm_small", &g_opt_lstm_small}, {"score_defer", &g_opt_score_defer}, {"score_sort", &g_opt_score_sort}, {"score_hist", &g_opt_score_hist}, {"score_i8", &g_opt_score_i8},
 };
 
-struct ProfPair { int site; hipEvent_t a, b; };
+struct ProfPair { int site; hipEvent_t a, b; int units; };      // units: launches' worth of work the bracket stands for
 static std::vector<ProfPair> g_pairs;          // recorded, not yet read
 static std::vector<hipEvent_t> g_free;         // recycled events
 static double g_total_ms[SITE_COUNT];
@@ -73,13 +76,13 @@ hipEvent_t prof_begin(hipStream_t st)
     if (e) (void)hipEventRecord(e, st);
     return e;
 }
-void prof_end(int site, hipEvent_t begin, hipStream_t st)
+void prof_end(int site, hipEvent_t begin, hipStream_t st, int units)
 {
     hipEvent_t e;
     { std::lock_guard<std::mutex> lk(g_prof_mu); e = take_event(); }
     if (e) (void)hipEventRecord(e, st);
     std::lock_guard<std::mutex> lk(g_prof_mu);
-    if (begin && e) g_pairs.push_back({site, begin, e});
+    if (begin && e) g_pairs.push_back({site, begin, e, units});
     else { if (begin) g_free.push_back(begin); if (e) g_free.push_back(e); }
 }
 
@@ -107,6 +110,9 @@ int opt_lstm_persist() { return g_opt_lstm_persist; }
 int opt_lstm_persist_min() { return g_opt_lstm_persist_min; }
 int opt_lstm_fast() { return g_opt_lstm_fast; }
 int opt_lstm_multi() { return g_opt_lstm_multi; }
+int opt_lstm_multi_min() { return g_opt_lstm_multi_min; }
+int opt_lstm_live_blocks() { return g_opt_lstm_live_blocks; }
+void note_lstm_multi_taken(int how) { g_opt_lstm_multi_taken = how; }
 int opt_lstm_persist_max() { return g_opt_lstm_persist_max; }
 int opt_lstm_persist_fault() { return g_opt_lstm_persist_fault; }
 int opt_vgg_fuse_pool() { return g_opt_vgg_fuse_pool; }
@@ -211,7 +217,10 @@ const char *vfr_last_error(void) { return vfr::g_err; }
 int vfr_set_option(const char *name, int value)
 {
     for (const auto &o : vfr::g_opts)
-        if (name && !strcmp(name, o.name)) { o.v->store(value); return VFR_OK; }
+        if (name && !strcmp(name, o.name)) {
+            if (o.v == &vfr::g_opt_lstm_multi_taken) return vfr::fail(VFR_EINVAL, "vfr_set_option: '%s' is read-only", name);
+            o.v->store(value); return VFR_OK;
+        }
     return vfr::fail(VFR_EINVAL, "vfr_set_option: unknown option '%s'", name ? name : "(null)");
 }
 int vfr_get_option(const char *name)
@@ -260,7 +269,7 @@ int vfr_profile_read(int site, double *total_ms, int64_t *launches, int reset)
     for (auto &p : vfr::g_pairs) {
         float ms = 0.0f;
         const hipError_t e = hipEventElapsedTime(&ms, p.a, p.b);
-        if (e == hipSuccess) { vfr::g_total_ms[p.site] += ms; vfr::g_launches[p.site] += 1; }
+        if (e == hipSuccess) { vfr::g_total_ms[p.site] += ms; vfr::g_launches[p.site] += p.units; }
         else if (e == hipErrorNotReady) { (void)hipGetLastError(); pending.push_back(p); continue; }
         else { (void)hipGetLastError(); ++failed; }
         vfr::g_free.push_back(p.a); vfr::g_free.push_back(p.b);

@@ -31,6 +31,9 @@ int opt_lstm_small4();
 int opt_lstm_persist();
 int opt_lstm_fast();
 int opt_lstm_multi();
+int opt_lstm_multi_min();
+int opt_lstm_live_blocks();
+void note_lstm_multi_taken(int how);   // read-only option "lstm_multi_taken" (vfr_capi.hip): which way the last vfr_bilstm_final_f32 went
 int opt_lstm_persist_min();
 int opt_lstm_persist_max();
 int opt_lstm_persist_fault();
@@ -63,11 +66,11 @@ enum Site : int {
 };
 bool profiling();
 hipEvent_t prof_begin(hipStream_t st);
-void prof_end(int site, hipEvent_t begin, hipStream_t st);
+void prof_end(int site, hipEvent_t begin, hipStream_t st, int units = 1);
 struct ProfScope {                       // owns its begin event: re-entrant across host threads, sites and streams
-    int site; hipStream_t st; bool on; hipEvent_t begin;
-    ProfScope(int s, hipStream_t t) : site(s), st(t), on(s != SITE_NONE && profiling()), begin(nullptr) { if (on) begin = prof_begin(st); }
-    ~ProfScope() { if (on) prof_end(site, begin, st); }
+    int site; hipStream_t st; bool on; hipEvent_t begin; int units;     // units: launches this bracket counts as (a kernel that does the work of T launches of its site)
+    ProfScope(int s, hipStream_t t, int n = 1) : site(s), st(t), on(s != SITE_NONE && profiling()), begin(nullptr), units(n) { if (on) begin = prof_begin(st); }
+    ~ProfScope() { if (on) prof_end(site, begin, st, units); }
     ProfScope(const ProfScope &) = delete;
     ProfScope &operator=(const ProfScope &) = delete;
 };
@@ -143,6 +146,9 @@ struct GemmArgs {
     // lstm_mcount[s] = number of active rows at step s (rows are sorted so the active set is a prefix); rows that join
     // at step s (>= lstm_mcount[s-1], or >= 1 at s = 0) take their incoming state from row 0, the all-pad row.
     const int *lstm_xrow; const int *lstm_mcount; int lstm_step;
+    // bit 0 (set by lstm_step_pair / lstm_steps_run from option "lstm_live_blocks"): a wave issues fragment reads, MFMAs, the
+    // table gather and the gate epilogue only for its LIVE 16-row blocks (a row below the active count, a unit below lstm_H)
+    int lstm_live;
     // input-projection table (lstm_tok != null, K == 0): the x-part of every gate chain depends only on the token, so it
     // is computed once per VOCABULARY entry (Cin = P [vocab, ldc], columns in the permuted tile order) and GEMM row m's
     // accumulators start from P[lstm_tok[m]] (the clamped token of row m's query at this step) -- the same chain,
@@ -150,6 +156,9 @@ struct GemmArgs {
     const int *lstm_tok;
     // training forward (nullable): the activated gates i, f, g, o of every row, [M, 4H] -- what the backward needs
     float *lstm_gates;
+    // DEBUG (nullable; option "lstm_live_blocks" bit 1): a counter the inference step adds its issued (16-row x 16-unit)
+    // MFMA blocks to -- tests compare it with the count the lengths imply; nothing is computed from it
+    unsigned *lstm_blocks;
 };
 int gemm_nt(const GemmArgs &g, hipStream_t st);
 // two GEMMs of identical shape as ONE grid (blockIdx.z picks the problem): fills the chip when one alone leaves a
@@ -161,7 +170,12 @@ int lstm_step_pair(const GemmArgs &g0, const GemmArgs &g1, hipStream_t st);
 // arguments (W2 / ldw2 / lda2 / biases / Cin + ldc = the projection table / M = rows / lstm_H / lstm_ldh / lstm_mcount for the
 // reverse direction); hbuf / cbuf = three rotating state buffers (buffer 0 zeroed; the final state is in buffer T % 3);
 // sync = lstm_steps_sync_words() zeroed words (word 8 = the error word: non-zero when the launch gave up).
+struct LstmPlan { bool one_launch; int tile; int64_t slots; };
+LstmPlan lstm_plan(int64_t R, int H, int T, int cus);      // gemm.hip: which form the fused steps take (options + shape, no device call)
 bool lstm_steps_supported(int64_t R, int H);
+// the one-launch kernel's workgroups wait for each other across XCD groups: true when its grid for R rows, T steps is resident
+// at once on the current device (occupancy x CUs); otherwise take the per-step launches
+bool lstm_steps_resident(int64_t R, int H, int T);
 size_t lstm_steps_sync_words(int64_t R, int T);
 int lstm_steps_run(const GemmArgs &g0, const GemmArgs &g1, float *const hbuf[3], float *const cbuf[3], const int *tokidx, const int *mcount,
                    unsigned *sync, int T, hipStream_t st);
