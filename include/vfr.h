@@ -306,6 +306,40 @@ int vfr_score_sentences_f32(const float *S, int64_t Ns, const float *V, const in
                             int64_t sent_base, int k, float *out_dist, int64_t *out_idx, int num_rank, const float *rank_dist,
                             const int64_t *rank_idx, int64_t *count_lt, int *bad, void *workspace, size_t workspace_bytes,
                             vfr_stream_t stream);
+/* ---- video-to-sentence retrieval (the reverse direction at the video level): which SENTENCES of a bank describe a whole VIDEO, and
+ * where its own sentences rank among them -- the video->text half of a two-way retrieval table, "caption / tag this video" from
+ * stored sentences.  S [Ns, D] = the sentence bank; videos int32 [Np] = CORPUS-GLOBAL video indices: they need not be sorted and
+ * may repeat; outputs are in the caller's order.
+ *   score(p, j) = b(j, v_p), the quantity of vfr_score_video_topk_f32 and vfr_score_paragraph_pairs_f32: the smallest moment score
+ *           over the WHOLE triangle of video v_p for sentence j, every moment score the canonical chain (k-ascending fp32 fma chain
+ *           of ((V - S) + eps)^2, IEEE sqrt, sequential fp32 sum s -> e, one IEEE division by (float)(e - s + 1)).  BIT-IDENTICAL to
+ *           the minimum over video v_p's block of row j of vfr_score_moments_f32(S, ..).  The moment that attains it, m(j, v) (the
+ *           smallest (distance, moment id) key, as in the video top-k), is NOT returned here: vfr_score_paragraph_pairs_f32 with
+ *           groups of length 1 gives it for named (sentence, video) pairs.
+ *           key = (fp32 bits of the score << 32) | (sent_base + j), order (distance, sentence id) ascending.
+ *   k > 0 : out_dist / out_idx [Np,k] = the k smallest keys over the bank's sentences as (distance, sent_base + j), padded with
+ *           (+inf, -1) when Ns < k.  k = 0 with counts only is allowed.
+ *   num_rank > 0 (<= 4): rank_dist / rank_idx / count_lt are [num_rank, Np]; count_lt[r][p] (int64) += number of sentences of this
+ *           bank whose key sorts strictly before (rank_dist[r][p], rank_idx[r][p]).  ADDED, so sentence-bank shards chain through
+ *           sent_base (the shard's first sentence id), and their lists merge with vfr_topk_merge_f32.
+ *   vid_base = global index of the clip bank's first video.  A probe whose video lies outside [vid_base, vid_base + Nv) belongs to
+ *           another shard and is skipped (padding, nothing added): every shard of a video-sharded bank takes the same probes.  A
+ *           video without clips gives padding, adds nothing and is not bad.
+ *   bad (nullable, device int): set to 1 for a probe with video < 0 (on any shard); such a probe gives padding and adds nothing.
+ *           Nothing is read before it is checked; nothing is read or written out of bounds.
+ * Exact arithmetic only: every (probe, sentence) pair gets its whole triangle.  An MFMA bounds pre-filter as the sentence->video
+ * direction has is not built for this one.  Any D (D = 100 with 16-byte aligned S and V takes the register-resident fast path).
+ * Np = 0, and k = 0 without rank keys and without bad, return without a launch.
+ * Limits: max_clips <= 64, k <= 448, sent_base + Ns < 2^32, Np * k < 2^31.  Bad host-side arguments: VFR_EINVAL before anything is
+ * enqueued; a short workspace: VFR_EWORKSPACE.
+ * vfr_score_video_sentences_workspace_bytes = 256 + 8 k Np C, C = min(ceil(2048 / Np), ceil(Ns / 64), 256) >= 1 = the bound on the
+ * chunks the sentence axis is cut into: O(Np k), no Np x Ns term (0 for a bad argument).                                  */
+size_t vfr_score_video_sentences_workspace_bytes(int64_t Np, int64_t Ns, int k);
+int vfr_score_video_sentences_f32(const float *S, int64_t Ns, const float *V, const int32_t *clip_offsets, int Nv, int total_clips,
+                                  int max_clips, int D, float eps, const int32_t *videos, int64_t Np, int64_t vid_base,
+                                  int64_t sent_base, int k, float *out_dist, int64_t *out_idx, int num_rank, const float *rank_dist,
+                                  const int64_t *rank_idx, int64_t *count_lt, int *bad, void *workspace, size_t workspace_bytes,
+                                  vfr_stream_t stream);
 /* ---- paragraph-to-video retrieval: which VIDEO does a group of sentences describe (the paragraph-to-video protocol of datasets
  * with several descriptions per video).  Q [Nq, D] = the sentences; a paragraph is a run of consecutive rows: grp_off [Ng+1]
  * (device int64, non-decreasing from 0 to Nq); max_len (host) = the longest run, <= 64.

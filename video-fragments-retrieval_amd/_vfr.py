@@ -67,6 +67,9 @@ SIGNATURES = {
     "vfr_score_sentences_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "vfr_score_sentences_f32": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32,
                                        _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vfr_score_video_sentences_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "vfr_score_video_sentences_f32": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _i64, _i64, _i32, _vp, _vp,
+                                             _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vfr_score_paragraphs_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "vfr_score_paragraphs_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _vp, _vp,
                                         _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
@@ -993,6 +996,37 @@ def score_sentences(S: torch.Tensor, bank: VideoBank, probes: torch.Tensor, k: i
             od, oi = torch.empty_like(od).index_copy_(0, order, od), torch.empty_like(oi).index_copy_(0, order, oi)
         if R:
             count_lt.index_add_(1, order, cl)
+    return od, oi, count_lt
+
+
+def score_video_sentences(S: torch.Tensor, bank: VideoBank, videos: torch.Tensor, k: int, vid_base: int = 0, sent_base: int = 0,
+                          rank_dist=None, rank_idx=None, count_lt=None, bad: torch.Tensor | None = None,
+                          workspace: torch.Tensor | None = None, eps: float = 1e-6):
+    """Video-to-sentence retrieval (include/vfr.h vfr_score_video_sentences_f32): per probe video the k best sentences of the bank
+    ``S`` [Ns, D], the score of (video, sentence) being the video's best moment distance for the sentence (``score_video_topk``'s
+    quantity).  ``videos`` [Np] int32 = corpus-global video indices, any order, repeats allowed; ``vid_base`` = global index of the
+    bank's first video (probes of other shards give padding and add nothing); ids are ``sent_base`` + row of ``S``.
+    rank_dist / rank_idx [R, Np] (or [Np]), R <= 4: ``count_lt`` [R, Np] int64 += the sentences that sort before each rank key
+    (allocated zeroed when None).  ``bad`` (device int32 [1], nullable) is set to 1 for a probe with video < 0.
+    Returns (dist [Np,k] | None, idx [Np,k] int64 | None, count_lt | None)."""
+    S = _dev(S, torch.float32, "S")
+    videos = _dev(videos, torch.int32, "videos")
+    if videos.dim() != 1:
+        raise RuntimeError(f"score_video_sentences: videos must be [Np], got {tuple(videos.shape)}")
+    if S.dim() != 2 or S.shape[1] != bank.dim:
+        raise RuntimeError(f"score_video_sentences: S must be [Ns, {bank.dim}], got {tuple(S.shape)}")
+    Ns, Np = int(S.shape[0]), int(videos.shape[0])
+    rank_dist, rank_idx, count_lt, R = _rank_keys(rank_dist, rank_idx, count_lt, Np, S.device)
+    if bad is not None:
+        bad = _dev(bad, torch.int32, "bad")
+    od, oi = _out_lists(Np, k, S.device)
+    nbytes = lib().vfr_score_video_sentences_workspace_bytes(Np, Ns, k)
+    workspace = _workspace(workspace, nbytes, S.device)
+    _check(lib().vfr_score_video_sentences_f32(_ptr(S) if Ns else 0, Ns, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.num_videos,
+                                               bank.total_clips, bank.max_clips, bank.dim, eps, _ptr(videos) if Np else 0, Np,
+                                               int(vid_base), int(sent_base), k, _ptr(od), _ptr(oi), R if Np else 0, _ptr(rank_dist),
+                                               _ptr(rank_idx), _ptr(count_lt), _ptr(bad), workspace.data_ptr(), nbytes, _stream()),
+           "vfr_score_video_sentences_f32")
     return od, oi, count_lt
 
 

@@ -1,4 +1,5 @@
-// Sentence retrieval for moments ("which sentences describe this moment"): vfr_score_sentences_f32 (include/vfr.h).
+// Sentence retrieval for moments ("which sentences describe this moment"): vfr_score_sentences_f32 (include/vfr.h), and for whole
+// videos ("which sentences describe this video"): vfr_score_video_sentences_f32, vsent_scan_kernel further down.
 //
 // The reverse direction of the scorers of score.hip / subset.hip: the PROBE (video, start clip, end clip) owns the list and the
 // sentences of the bank are ranked.  score(m, j) is the canonical chain of vfr_score_moments_f32 (k-ascending fp32 fma chain over
@@ -207,6 +208,123 @@ __global__ __launch_bounds__(64) void sentences_scan_kernel(const float *__restr
     }
 }
 
+// ---- video -> sentences (vfr_score_video_sentences_f32): one wave per (probe video, chunk of the sentence axis), lane = sentence ----
+// score(p, j) = b(j, v_p): the smallest moment score over the WHOLE triangle of the probe's video.  The lane's n clip distances go to its
+// LDS column as above (sen_dist_fast: the row in registers, the clip rows wave-uniform), then the lane walks the triangle -- per start
+// clip a running fp32 sum over the end clip and one IEEE division per moment -- and keeps the smallest score bits.  m(j, v), the moment
+// that attains it, is not returned by this call, and among equal scores every moment gives the same sentence key, so no moment position
+// is carried along.  Rank counts and the list state are wave-uniform and live in registers (one probe per wave).
+constexpr int VSENT_TARGET_WAVES = 2048;            // a guess, as SEN_TARGET_WAVES
+
+template <bool FAST>
+__global__ __launch_bounds__(64) void vsent_scan_kernel(const float *__restrict__ S, int64_t Ns, const float *__restrict__ V,
+                                                        const int32_t *__restrict__ clip_off, int Nv, int total_clips, int D, float eps,
+                                                        const int32_t *__restrict__ videos, int64_t Np, int64_t vid_base,
+                                                        int64_t sent_base, int k, int cap, ScanRank rk, int rows, int chunks,
+                                                        int64_t per, int *__restrict__ bad, unsigned long long *__restrict__ ws)
+{
+    extern __shared__ __attribute__((aligned(16))) float ssm[];
+    float *ds = ssm;                                                                       // [rows][64] clip distances, lane-minor
+    unsigned long long *buf = reinterpret_cast<unsigned long long *>(ssm + (size_t)rows * 64);   // [cap]
+    const int lane = threadIdx.x;
+    const int64_t p = blockIdx.x / chunks;
+    const int ch = (int)(blockIdx.x - p * chunks);
+    const int64_t j0 = (int64_t)ch * per;
+    const int64_t j1 = j0 + per < Ns ? j0 + per : Ns;
+
+    // the probe's video, checked before anything of the bank is read: n = 0 gives padding and adds nothing
+    const int gv = uni(videos[p]);
+    int n = 0, c0 = 0;
+    const int64_t l = (int64_t)gv - vid_base;
+    if (gv >= 0 && l >= 0 && l < Nv) {
+        const int a = uni(clip_off[l]);
+        int m = uni(clip_off[l + 1]) - a;
+        m = m > rows ? rows : m;
+        if (m > 0 && a >= 0 && a <= total_clips - m) { n = m; c0 = a; }     // the clip rows a .. a + m lie inside V
+    }
+    if (gv < 0 && bad && ch == 0 && lane == 0) *bad = 1;
+
+    unsigned long long rkey[SCAN_MAX_RANK];
+#pragma unroll
+    for (int r = 0; r < SCAN_MAX_RANK; ++r)
+        rkey[r] = r < rk.num_rank ? make_key(rk.dist[r * Np + p], (unsigned)rk.idx[r * Np + p]) : 0ull;
+    unsigned nlt[SCAN_MAX_RANK] = {0u, 0u, 0u, 0u};            // wave-uniform: a chunk holds fewer than 2^32 sentences
+
+    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    unsigned long long thr = SCAN_KEY_MAX;                     // keys >= thr cannot be among the chunk's k smallest
+    int cnt = 0;                                               // keys in buf (wave-uniform)
+    const float *vb = V + (int64_t)c0 * D;
+
+    for (int64_t jb = j0; jb < j1 && n > 0; jb += 64) {
+        const int64_t j = jb + lane;
+        const bool live = j < j1;
+        const float *sr = S + (live ? j : j1 - 1) * D;
+        int c = 0;
+        if constexpr (FAST) {
+            float4 x[SCAN_FAST_D / 4];
+#pragma unroll
+            for (int k4 = 0; k4 < SCAN_FAST_D / 4; ++k4) x[k4] = *reinterpret_cast<const float4 *>(sr + 4 * k4);
+            for (; c + 4 <= n; c += 4) sen_dist_fast<4>(x, vb + (int64_t)c * SCAN_FAST_D, eps, ds + c * 64 + lane);
+            for (; c < n; ++c) sen_dist_fast<1>(x, vb + (int64_t)c * SCAN_FAST_D, eps, ds + c * 64 + lane);
+        } else {
+            for (; c < n; ++c) {
+                const float *vr = vb + (int64_t)c * D;
+                float acc = 0.0f;
+                for (int kk = 0; kk < D; ++kk) {
+                    const float t = (vr[kk] - sr[kk]) + eps;
+                    acc = __builtin_fmaf(t, t, acc);
+                }
+                ds[c * 64 + lane] = __builtin_sqrtf(acc);
+            }
+        }
+        // the whole triangle from the lane's own column: scores are >= 0, so their bits order as they do
+        unsigned best = 0xFFFFFFFFu;
+        for (int s = 0; s < n; ++s) {
+            float sum = 0.0f;
+            for (int e = s; e < n; ++e) {
+                const float de = ds[e * 64 + lane];
+                sum = e == s ? de : sum + de;
+                const unsigned b = __float_as_uint(sum / (float)(e - s + 1));
+                best = b < best ? b : best;
+            }
+        }
+        const unsigned long long key = ((unsigned long long)best << 32) | (unsigned)(sent_base + j);
+#pragma unroll
+        for (int r = 0; r < SCAN_MAX_RANK; ++r) {
+            if (r < rk.num_rank) nlt[r] += (unsigned)__popcll(__ballot(live && key < rkey[r]));
+        }
+        if (k > 0) {
+            const bool take = live && key < thr;
+            const unsigned long long mt = __ballot(take);
+            if (mt) {
+                if (take) buf[cnt + __popcll(mt & below)] = key;
+                cnt += __popcll(mt);
+                if (cnt > cap - 64) {
+                    __syncthreads();
+                    wave_sort_keys(buf, cnt, cap, lane);
+                    if (cnt >= k) { thr = buf[k - 1]; cnt = k; }
+                    __syncthreads();
+                }
+            }
+        }
+    }
+    if (k > 0) {
+        __syncthreads();
+        int size = 64;
+        while (size < cnt) size <<= 1;                         // cnt <= cap, a power of two
+        wave_sort_keys(buf, cnt, size, lane);
+        cnt = cnt > k ? k : cnt;
+        unsigned long long *out = ws + ((size_t)ch * Np + p) * k;
+        for (int i = lane; i < k; i += 64) out[i] = i < cnt ? buf[i] : SCAN_KEY_EMPTY;
+    }
+    if (lane < rk.num_rank) {
+        unsigned x = nlt[0];
+#pragma unroll
+        for (int r = 1; r < SCAN_MAX_RANK; ++r) x = lane == r ? nlt[r] : x;
+        if (x) atomicAdd(reinterpret_cast<unsigned long long *>(rk.count_lt + (int64_t)lane * Np + p), (unsigned long long)x);
+    }
+}
+
 }  // namespace
 }  // namespace vfr
 
@@ -263,6 +381,60 @@ int vfr_score_sentences_f32(const float *S, int64_t Ns, const float *V, const in
     }
     if (k > 0)
         return vfr_topk_merge_keys(reinterpret_cast<const int64_t *>(keys), plan.chunks, Nm, k, out_dist, out_idx, nullptr, stream);
+    return VFR_OK;
+}
+
+size_t vfr_score_video_sentences_workspace_bytes(int64_t Np, int64_t Ns, int k)
+{
+    if (Np < 0 || Ns < 0 || k < 0 || k > vfr::SCAN_MAX_K || Np * (int64_t)(k > 0 ? k : 1) > 0x7FFFFFFF) return 0;
+    const vfr::ScanPlan p = vfr::scan_plan(Np, Ns, vfr::VSENT_TARGET_WAVES);
+    return vfr::align_up((size_t)p.bound * (size_t)Np * (size_t)k * 8 + 256, 256);
+}
+
+int vfr_score_video_sentences_f32(const float *S, int64_t Ns, const float *V, const int32_t *clip_offsets, int Nv, int total_clips,
+                                  int max_clips, int D, float eps, const int32_t *videos, int64_t Np, int64_t vid_base,
+                                  int64_t sent_base, int k, float *out_dist, int64_t *out_idx, int num_rank, const float *rank_dist,
+                                  const int64_t *rank_idx, int64_t *count_lt, int *bad, void *workspace, size_t workspace_bytes,
+                                  vfr_stream_t stream)
+{
+    VFR_REQUIRE(Ns >= 0 && Np >= 0 && Nv >= 0 && total_clips >= 0 && D > 0 && k >= 0 && k <= vfr::SCAN_MAX_K && max_clips >= 0 &&
+                max_clips <= vfr::SEN_MAX_CLIPS && vid_base >= 0 && sent_base >= 0, VFR_EINVAL,
+                "vfr_score_video_sentences_f32: bad shape (k <= 448, max_clips <= 64, sizes, vid_base, sent_base >= 0)");
+    VFR_REQUIRE(sent_base + Ns < (int64_t(1) << 32), VFR_EINVAL, "vfr_score_video_sentences_f32: sent_base + Ns must stay below 2^32");
+    VFR_REQUIRE(Np * (int64_t)(k > 0 ? k : 1) <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_video_sentences_f32: Np * k must stay below 2^31");
+    VFR_REQUIRE(num_rank >= 0 && num_rank <= vfr::SCAN_MAX_RANK, VFR_EINVAL, "vfr_score_video_sentences_f32: num_rank %d (0 .. 4)",
+                num_rank);
+    VFR_REQUIRE(num_rank == 0 || (rank_dist && rank_idx && count_lt), VFR_EINVAL,
+                "vfr_score_video_sentences_f32: num_rank > 0 needs rank_dist, rank_idx and count_lt");
+    VFR_REQUIRE(k == 0 || Np == 0 || (out_dist && out_idx), VFR_EINVAL, "vfr_score_video_sentences_f32: k > 0 needs out_dist / out_idx");
+    VFR_REQUIRE(Np == 0 || videos, VFR_EINVAL, "vfr_score_video_sentences_f32: videos is null");
+    VFR_REQUIRE(Ns == 0 || S, VFR_EINVAL, "vfr_score_video_sentences_f32: S is null");
+    VFR_REQUIRE(Nv == 0 || (clip_offsets && (V || total_clips == 0)), VFR_EINVAL, "vfr_score_video_sentences_f32: null clip bank");
+    const vfr::ScanPlan plan = vfr::scan_plan(Np, Ns, vfr::VSENT_TARGET_WAVES);
+    VFR_REQUIRE(Np * plan.chunks <= 0x7FFFFFFF, VFR_EINVAL, "vfr_score_video_sentences_f32: too many probes");
+    const size_t need = vfr_score_video_sentences_workspace_bytes(Np, Ns, k);
+    VFR_REQUIRE(workspace && workspace_bytes >= need, VFR_EWORKSPACE, "vfr_score_video_sentences_f32: workspace %zu < %zu bytes",
+                workspace_bytes, need);
+    if (Np == 0 || (k == 0 && num_rank == 0 && !bad)) return VFR_OK;
+    hipStream_t st = vfr::as_stream(stream);
+    const int rows = max_clips < 1 ? 1 : max_clips;
+    const int cap = vfr::scan_cap(k);
+    const size_t lds = (size_t)rows * 64 * 4 + (size_t)cap * 8;                          // <= 16 KB + 4 KB
+    unsigned long long *keys = static_cast<unsigned long long *>(workspace);
+    {
+        vfr::ProfScope prof(vfr::SITE_SCORE_PAIRS, st);
+        vfr::ScanRank rk{num_rank, rank_dist, rank_idx, count_lt};
+        const dim3 grid((unsigned)(Np * plan.chunks)), block(64);
+        if (vfr::rows_fast(S, V, D))
+            hipLaunchKernelGGL((vfr::vsent_scan_kernel<true>), grid, block, lds, st, S, Ns, V, clip_offsets, Nv, total_clips, D, eps,
+                               videos, Np, vid_base, sent_base, k, cap, rk, rows, plan.chunks, plan.per, bad, keys);
+        else
+            hipLaunchKernelGGL((vfr::vsent_scan_kernel<false>), grid, block, lds, st, S, Ns, V, clip_offsets, Nv, total_clips, D, eps,
+                               videos, Np, vid_base, sent_base, k, cap, rk, rows, plan.chunks, plan.per, bad, keys);
+        VFR_CHECK_LAUNCH("vsent_scan_kernel");
+    }
+    if (k > 0)
+        return vfr_topk_merge_keys(reinterpret_cast<const int64_t *>(keys), plan.chunks, Np, k, out_dist, out_idx, nullptr, stream);
     return VFR_OK;
 }
 

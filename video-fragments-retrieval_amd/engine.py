@@ -69,6 +69,11 @@ class HipOps:
         return self.v.score_sentences(S, bank, probes, k, vid_base, sent_base, rank_dist, rank_idx, count_lt=count_lt, bad=bad,
                                       workspace=workspace)
 
+    def score_video_sentences(self, S, bank, videos, k, vid_base=0, sent_base=0, rank_dist=None, rank_idx=None, count_lt=None,
+                              bad=None, workspace=None):
+        return self.v.score_video_sentences(S, bank, videos, k, vid_base, sent_base, rank_dist, rank_idx, count_lt=count_lt, bad=bad,
+                                            workspace=workspace)
+
     def score_paragraphs(self, Q, bank, grp_off, max_len, k, vid_base=0, own_dist=None, own_idx=None, count=None, workspace=None,
                          bad=None):
         return self.v.score_paragraphs(Q, bank, grp_off, max_len, k, vid_base, own_dist, own_idx, count=count, workspace=workspace,
@@ -1395,6 +1400,77 @@ def corpus_paragraph_topk(shard: CorpusShard, Q, groups: ParagraphGroups, k, own
     return od, oi, cnt, moments
 
 
+def corpus_video_sentence_topk(shard: CorpusShard, S, videos, k, own_off=None, own_rows=None, ground=False, ops=None, world=1,
+                               workspace=None):
+    """Video-to-sentence retrieval over the corpus: per probe video (``videos`` [Np]: global video indices, host array-like, any
+    order, repeats allowed) the k sentences of the bank ``S`` [Ns, D] with the smallest score = the video's best moment distance for
+    the sentence (``corpus_video_topk``'s quantity), in (score, sentence index) order.  With ``own_off`` [Np+1] / ``own_rows`` (a CSR
+    of the rows of ``S`` that belong to each probe) also the 0-based rank of the probe's best-ranked own sentence = the number of
+    sentences whose key sorts strictly before the smallest own key; the own distances come from one pairs launch (groups of
+    length 1) on the rank that holds the video, MIN-reduced.  A probe without own rows gets rank -1; a probe whose video has no
+    clips (or is out of range) scores nothing, so its rank is 0.  ``ground``: also the global id of the moment of the probe video
+    that each returned sentence lands on (-1 for padding), from one pairs launch on the merged result, MAX-reduced.  ``world`` > 1:
+    the clip bank is sharded by video, ``S`` is replicated and every rank passes the same probes; the lists merge with the key
+    merge and the counts add.
+    Returns (dist [Np,k], sentence index [Np,k] int64 (-1 = padding), ranks [Np] int64 | None, moments [Np,k] int64 | None);
+    dist / index are None for k = 0."""
+    ops = ops or HipOps()
+    vids = np.asarray(videos.cpu() if isinstance(videos, torch.Tensor) else videos, np.int64).reshape(-1)
+    Np, Ns, dev = len(vids), int(S.shape[0]), shard.device
+    if Np and (vids.min() < -(1 << 31) or vids.max() >= (1 << 31)):
+        raise ValueError("corpus_video_sentence_topk: video index outside int32")
+    dist = _group(world)
+    vids_t = torch.from_numpy(vids.astype(np.int32)).to(dev)
+    rd = ri = has = None
+    if (own_off is None) != (own_rows is None):
+        raise ValueError("corpus_video_sentence_topk: give own_off and own_rows together")
+    if own_off is not None:
+        off = np.asarray(own_off.cpu() if isinstance(own_off, torch.Tensor) else own_off, np.int64).reshape(-1)
+        rows = np.asarray(own_rows.cpu() if isinstance(own_rows, torch.Tensor) else own_rows, np.int64).reshape(-1)
+        if len(off) != Np + 1 or off[0] != 0 or off[-1] != len(rows) or (np.diff(off) < 0).any():
+            raise ValueError(f"corpus_video_sentence_topk: own_off must be a non-decreasing run [Np + 1] from 0 to {len(rows)}")
+        if len(rows) and (rows.min() < 0 or rows.max() >= Ns):
+            raise ValueError(f"corpus_video_sentence_topk: own_rows out of range [0, {Ns})")
+        lens = np.diff(off)
+        has = torch.from_numpy(lens > 0).to(dev)
+        key = torch.full((Np,), KEY_INF & ~0xFFFFFFFF, dtype=torch.int64, device=dev)      # (+inf, 0): no own row
+        if len(rows):
+            nnz = len(rows)
+            probe = np.repeat(np.arange(Np), lens)
+            rows_t = torch.from_numpy(rows).to(dev)
+            pairs = torch.from_numpy(np.stack([np.arange(nnz), vids[probe]], axis=1).astype(np.int32)).to(dev)
+            one = torch.arange(nnz + 1, dtype=torch.int64, device=dev)
+            own_d, _ = ops.score_paragraph_pairs(S[rows_t].contiguous(), shard.bank, one, 1, pairs, shard.lo, moments=False)
+            if dist is not None:
+                dist.all_reduce(own_d, op=dist.ReduceOp.MIN)
+            best = torch.full((Np,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=dev)
+            best.scatter_reduce_(0, torch.from_numpy(probe).to(dev), _pack_key(own_d, rows_t), reduce="amin")
+            key = torch.where(has, best, key)
+        if Np:                                                # (no probes: no keys, and the ranks are an empty tensor)
+            rd, ri = _unpack_key(key)
+            rd, ri = rd.contiguous(), ri.contiguous()
+    od, oi, cnt = _exchange(*ops.score_video_sentences(S, shard.bank, vids_t, k, shard.lo, 0, rd, ri, workspace=workspace), k, ops, world)
+    ranks = None
+    if cnt is not None:
+        ranks = torch.where(has, cnt[0], torch.full_like(cnt[0], -1))
+    elif has is not None:
+        ranks = torch.zeros((0,), dtype=torch.int64, device=dev)
+    moments = None
+    if ground and k > 0:
+        moments = torch.full((Np * k,), -1, dtype=torch.int64, device=dev)
+        if Np:
+            flat = oi.reshape(-1)
+            gv = torch.where(flat >= 0, vids_t.to(torch.int64).repeat_interleave(k), torch.full_like(flat, -1))
+            pairs = torch.stack([torch.arange(Np * k, device=dev), gv], dim=1).to(torch.int32).contiguous()
+            one = torch.arange(Np * k + 1, dtype=torch.int64, device=dev)
+            _, mom = ops.score_paragraph_pairs(S[flat.clamp(min=0)].contiguous(), shard.bank, one, 1, pairs, shard.lo)
+            moments = mom.reshape(-1)
+            if dist is not None:
+                dist.all_reduce(moments, op=dist.ReduceOp.MAX)
+        moments = moments.reshape(Np, k)
+    return od, oi, ranks, moments
+
+
 def video_results(ids, dist, names, counts_all, mom_off_all):
     """Search results as rows: per query a list of (video name, start_t, end_t, distance) for the global moment ids ``ids``
     [Nq, k] (``corpus_video_topk`` / ``corpus_topk``); start_t / end_t are the inclusive clip span of the moment
@@ -1882,6 +1958,35 @@ class TorchCpuOps:
                 acc = acc + d[:, c]
             out[m] = _pack_key(acc / float(e0 - s0 + 1), ids)
         kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nm), rank_idx.reshape(-1, Nm))
+        return self._topk_lists(out, k) + (self._counts_below(out, kstar, count_lt),)
+
+    def score_video_sentences(self, S, bank, videos, k, vid_base=0, sent_base=0, rank_dist=None, rank_idx=None, count_lt=None,
+                              bad=None, workspace=None, eps=1e-6):
+        """Video-to-sentence retrieval from dense torch arithmetic (same semantics and bits as ``_vfr.score_video_sentences``): per
+        probe video the smallest moment score of every sentence of ``S`` over the video's whole triangle, keys (score, sent_base +
+        row), the k smallest, and the keys below each rank key.  Probes of other shards or on a video without clips give padding
+        and add nothing; a video < 0 sets ``bad``."""
+        S = S.float()
+        Ns = S.shape[0]
+        vids = [int(x) for x in torch.as_tensor(videos).reshape(-1).tolist()]
+        Np = len(vids)
+        off = bank.clip_off.tolist()
+        Nv = len(off) - 1
+        ids = sent_base + torch.arange(Ns)
+        out = torch.full((Np, Ns), KEY_INF, dtype=torch.int64)          # a probe without keys here: padding, nothing below
+        best = {}                                                        # local video -> [Ns] best distances, once per video
+        for p, gv in enumerate(vids):
+            if gv < 0:
+                if bad is not None:
+                    bad.fill_(1)
+                continue
+            lv = gv - vid_base
+            if lv < 0 or lv >= Nv or off[lv + 1] <= off[lv] or Ns == 0:
+                continue
+            if lv not in best:
+                best[lv] = self._video_scores(self._clip_dist(S, bank.emb[off[lv]:off[lv + 1]], eps)).min(dim=1).values
+            out[p] = _pack_key(best[lv], ids)
+        kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Np), rank_idx.reshape(-1, Np))
         return self._topk_lists(out, k) + (self._counts_below(out, kstar, count_lt),)
 
     def _span_scores(self, Q, bank, items, vid_base, bad, eps=1e-6):

@@ -390,6 +390,34 @@ def evaluate_paragraphs(model, video_iterator, lang_iterator, annotations, devic
     return out
 
 
+def evaluate_video_sentences(model, video_iterator, lang_iterator, annotations, device, atk=(1, 5, 10, 50), rank=0, world=1,
+                             return_topk=0):
+    """Video-to-sentence retrieval metrics of the same iterators ``evaluate`` consumes (the video -> text half of a two-way
+    retrieval table): given a whole video, where do its own sentences rank among ALL sentences of ``lang_iterator``.
+
+    One probe per video that has queries, in video order; the sentence bank is every query of ``lang_iterator`` in iteration
+    order.  The score of (video, sentence) is the video's best moment distance for the sentence (``evaluate_videos``' quantity);
+    the 0-based rank of a video is that of its best-ranked own sentence = the number of sentences whose (score, sentence index)
+    key sorts before its smallest own key (``engine.corpus_video_sentence_topk``).  Returns ``{"video_sentence": {"R@1", "R@5",
+    "R@10", "R@50", "MR"}}`` (``get_metrics``, as ``evaluate_videos``); with ``return_topk`` = k also ``(dist, sentence idx, probe
+    videos)``: [Np, k] lists of the k best sentences per probe and the global video index [Np] of each probe.  Labels, IoU and
+    annotation times play no part."""
+    with _eval_mode(model):
+        ops, _, _, shard, names, S, own = _prepare(model, video_iterator, lang_iterator, device, rank, world)
+        if shard is None:
+            out = {"video_sentence": get_metrics(_empty_metrics(atk))}
+            return (out, (None, None, None)) if return_topk else out
+        rows = np.argsort(own, kind="stable")                 # the bank rows grouped by their video: a CSR over the probes
+        videos, lengths = np.unique(own, return_counts=True)
+        off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        dist, idx, ranks, _ = engine.corpus_video_sentence_topk(shard, S, videos, int(return_topk), off, rows, ops=ops, world=world)
+        ranks = ranks.cpu().numpy()
+    out = {"video_sentence": get_metrics(_rank_metrics(ranks, atk))}
+    if return_topk:
+        return out, (dist, idx, videos)
+    return out
+
+
 def _fusion_streams(models, video_iterators, lang_iterators, device, rank, world, who):
     """The streams of a late fusion, encoded: one ``_prepare`` per (model, video iterator, language iterator); every stream must
     iterate the queries of stream 0 in its order (ValueError).  Returns (ops, annot_ids, own, shards, names per stream, Qs);
