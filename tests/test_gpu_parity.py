@@ -899,7 +899,7 @@ def test_bilstm_few_queries_vector_chain(vfr, oracle, normlang):
 @pytest.mark.gpu
 @pytest.mark.parametrize("normlang", [False, True])
 def test_bilstm_mid_batches_sequence_kernel(vfr, oracle, normlang):
-    """3-64 queries at the model's shape run the whole BiLSTM sequence in ONE launch on the matrix pipe (lstm_seq_mfma_kernel:
+    """3-32 queries at the model's shape run the whole BiLSTM sequence in ONE launch on the matrix pipe (lstm_seq_mfma_kernel:
     weights in registers as MFMA B fragments, h handed between workgroups as tagged granules): same bits as the MFMA tile
     steps (`lstm_persist` 0) and as the oracle; one and two row tiles, batches that do not fill a tile, an all-pad query,
     repeated calls (the granule buffers are re-zeroed every call)."""
@@ -911,12 +911,8 @@ def test_bilstm_mid_batches_sequence_kernel(vfr, oracle, normlang):
     rest = (dev(sd["word_embedding.weight"]), {k: dev(v) for k, v in lstm_of(sd).items()}, dev(sd["lang_fc.weight"]),
             dev(sd["lang_fc.bias"]), dev(lt) if lt is not None else None)
     want = oracle.bilstm_final(tokens, sd["word_embedding.weight"], lstm_of(sd), sd["lang_fc.weight"], sd["lang_fc.bias"], lt)
-    for B in (3, 8, 16, 17, 32, 33, 49, 64):            # (above 32: two parts taking turns on the same resident weights -- an
-        vfr.set_option("lstm_persist_max", 64)           #  option, slower than the tile steps there: default limit 32)
-        try:
-            seq = vfr.bilstm_final(dev(tokens[:B]), *rest)
-        finally:
-            vfr.set_option("lstm_persist_max", 32)
+    for B in (3, 8, 16, 17, 32, 33, 49, 64):            # (above 32: the tile steps)
+        seq = vfr.bilstm_final(dev(tokens[:B]), *rest)
         try:
             vfr.set_option("lstm_persist", 0)
             tiles = vfr.bilstm_final(dev(tokens[:B]), *rest)
@@ -1091,25 +1087,19 @@ def test_bilstm_tile_shapes_agree(vfr, oracle):
 
 
 @pytest.mark.gpu
-def test_gemm_ping_pong_variant_is_bit_identical(vfr):
-    """The experimental ping-pong schedule (two tile groups per 512-thread workgroup) walks k in the same order."""
+def test_gemm_large_grid_mfma_equals_valu(vfr):
+    """A dense GEMM whose grid is large (33 x 17 tiles of 128 rows: the 64-row form of the large launches, K <= 2048) gives the
+    VALU kernel's bits (`gemm` 0), bias and ReLU included."""
     rs = np.random.RandomState(3)
     A, W, b = (dev(rs.randn(4100, 512).astype(np.float32)), dev(rs.randn(2050, 512).astype(np.float32)),
                dev(rs.randn(2050).astype(np.float32)))
-    sd = synth.model_weights(4096, seed=7)
-    tokens = synth.query_tokens(1500, seed=7)
-    args = (dev(tokens), dev(sd["word_embedding.weight"]), {k: dev(v) for k, v in lstm_of(sd).items()},
-            dev(sd["lang_fc.weight"]), dev(sd["lang_fc.bias"]))
-    out = {}
+    mfma = vfr.linear(A, W, b, relu=True)
     try:
-        for pp in (0, 1):
-            vfr.set_option("gemm_pp", pp)
-            vfr.set_option("lstm_tile", 2)
-            out[pp] = (vfr.linear(A, W, b, relu=True), vfr.bilstm_final(*args))
+        vfr.set_option("gemm", 0)
+        valu = vfr.linear(A, W, b, relu=True)
     finally:
-        vfr.set_option("gemm_pp", 0)
-        vfr.set_option("lstm_tile", 0)
-    assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
+        vfr.set_option("gemm", 1)
+    assert torch.equal(mfma, valu)
 
 
 @pytest.mark.gpu

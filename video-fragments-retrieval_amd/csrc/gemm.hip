@@ -94,40 +94,10 @@ __global__ __launch_bounds__(256) void gemm_nt_valu(GemmArgs g)
 // LDS returns compete with the 32x32x2 accumulator write-back (64 B/clk), whatever the prefetch distance or spreading, while
 // 16x16x4 writes back half as much per flop.  fp32 MFMA runs at the fp32 vector rate (32 cycles per 16x16x4 per SIMD).
 // ------------------------------------------------------------------------------------------------
-#ifndef VFR_LSTM_NBUF
-#define VFR_LSTM_NBUF 2      // the fused LSTM step's own choice (experiment switch)
-#endif
-#ifndef VFR_GLOAD_SLICE
-#define VFR_GLOAD_SLICE 3      /* k-slice of a K-tile after which the global loads of K-tile kt+2 are issued (1, 2: within run-to-run noise) */
-#endif
-#ifndef VFR_GEMM_PIPE
-#define VFR_GEMM_PIPE 1      // 1: K-tile loop software-pipelined across the tile boundary (see the main loop); 0: the plain loop
-#endif
-#ifndef VFR_LSTM_DEPTH
-#ifndef VFR_LSTM_CELL_EARLY
-#define VFR_LSTM_CELL_EARLY 1   // 1: the gate epilogue's loads (previous cell state, biases) are requested at the head of the tile; 0: at the head of the epilogue
-#endif
-#define VFR_LSTM_DEPTH 1     // fragment prefetch distance (k-slices) of the fused LSTM step; the other MFMA kernels use 2
-#endif
-#ifndef VFR_LSTM_WAVES
-#define VFR_LSTM_WAVES 2
-#endif
-#ifndef VFR_GEMM_NBUF
-#define VFR_GEMM_NBUF 2      // LDS tile buffers: 2 = double buffered (2 workgroups/CU), 1 = single (3 workgroups/CU)
-#endif
-#ifndef VFR_GEMM_SETPRIO
-#define VFR_GEMM_SETPRIO 0
-#endif
-#ifndef VFR_GEMM_SPREAD
-#define VFR_GEMM_SPREAD 2    // 2: staging stores interleaved 1:1 with the MFMAs of slices 1-2, order pinned (see the K-tile loop); 1: interleaved, order left to the scheduler; 0: one block behind slice 1
-#endif
-#ifndef VFR_GEMM_DEEP
-#define VFR_GEMM_DEEP 0      // 1: two staging register sets, K-tiles kt + 2 and kt + 3 in flight (see DEEP in the kernel body); 0: one.
-                             // EXPERIMENT (round 3): bit-identical, +20..32 VGPRs, and no faster anywhere -- the fused LSTM step at 64 / 200 /
-                             // 625 / 1250 / 5000 queries 0.745 / 0.953 / 1.80 / 3.10 / 10.09 ms per pass against 0.730 / 0.955 / 1.81 / 3.09 /
-                             // 10.16 with one set: the small-batch step is not waiting for its staging loads (nor for its fragment reads:
-                             // VFR_LSTM_DEPTH 2 changes nothing either).  Off.
-#endif
+// Schedule constants of the pipelined K-tile loop.  The other settings of each were built, measured no better and deleted
+// (HISTORY.md keeps the numbers).
+constexpr int GLOAD_SLICE = 3;     // k-slice of a K-tile after which the global loads of K-tile kt+2 are issued (1, 2: within run-to-run noise)
+constexpr int LSTM_DEPTH = 1;      // fragment prefetch distance (k-slices) of the fused LSTM step: 1.5 % faster than the 2 of the other MFMA kernels
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int MBM = 128, MBN = 128, MBK = 32, MLD_PAD = 36;
 
@@ -158,16 +128,8 @@ __device__ unsigned long long g_gemm_stamps[4];
 // MI = 32-row MFMA tiles per wave along M: 2 -> 128-row workgroup tile, 1 -> 64-row tile (half the work per workgroup, for
 // launches whose 128-row grid would leave most of the chip idle or waiting on a second, nearly empty round)
 //
-// PP = ping-pong schedule (EXPERIMENT, off by default: vfr_set_option("gemm_pp", 1)).  A 512-thread workgroup holds two
-// independent 4-wave tile groups (one wave of each on every SIMD) whose phases are interleaved by workgroup barriers -- group
-// 0 runs the MFMA block of K-tile k while group 1 writes its K-tile k+1 to LDS and issues the loads of k+2, then they swap --
-// so every SIMD always has exactly one MFMA stream and a group needs a single LDS buffer.  The idea: two free-running
-// workgroups per CU pull each other into lock step (the one behind gets the whole matrix pipe while the other loads) and the
-// pipe then idles through both load blocks (PMC: 77 % occupancy dense, 59 % LSTM step).  Measured: bit-identical results but
-// SLOWER (dense 122 -> 98 TF, LSTM step 0.66 -> 0.79 ms): in-kernel stamps put 38 % of a wave's time in its MFMA blocks, 27 %
-// in its (tiny) load blocks and 25 % at the barriers -- the load block of one group crawls beside the other group's MFMA
-// block (raising that block's wave priority with s_setprio changes nothing).  Kept as a switchable variant for the next round's
-// work on that stall.
+// (A ping-pong schedule -- two tile groups per 512-thread workgroup taking turns on the matrix pipe -- was built, measured
+// slower and deleted: HISTORY.md.)
 // NARROW = 64-column workgroup tile, the four waves stacked along M (each wave still 16*TI x 64): for operands with N <= 64
 // (VGG conv1_1 / conv1_2), where the 128-column tile would spend half of every MFMA on columns that do not exist.
 // LFAST = the fused LSTM step in the shape the bench and the model run it: chains start from the projection table (K == 0: one
@@ -184,15 +146,15 @@ __device__ unsigned long long g_gemm_stamps[4];
 // trust this XCD's L2), because the producer of a row's h ran on another XCD in the SAME launch.  The weights and the
 // projection table are read-only and keep the plain (L2-resident) path.
 typedef unsigned int vfr_u32x4 __attribute__((ext_vector_type(4)));
-template <bool VEC, bool CONV, bool LSTM = false, int MI = 2, bool PP = false, bool NARROW = false, bool TRAIN = false, bool CFAST = false, bool LFAST = false, bool CHALO = false, bool MULTI = false>
+template <bool VEC, bool CONV, bool LSTM = false, int MI = 2, bool NARROW = false, bool TRAIN = false, bool CFAST = false, bool LFAST = false, bool CHALO = false, bool MULTI = false>
 __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by = 0, int64_t task_m0 = 0, int task_tid = 0)
 {
     static_assert(!MULTI || (LFAST && !TRAIN), "MULTI: the table-start LSTM step inside the multi-step kernel");
     static_assert(!CFAST || CONV, "CFAST: the convolution loader for C_in a multiple of 32");
     static_assert(!CHALO || CFAST, "CHALO: the scalar-tap loader on halo-padded activations");
-    static_assert(!LFAST || (LSTM && !PP), "LFAST: the table-start LSTM step");
+    static_assert(!LFAST || LSTM, "LFAST: the table-start LSTM step");
     static_assert(!TRAIN || LSTM, "TRAIN: the fused LSTM step that also stores its gates");
-    static_assert(!NARROW || (MI == 1 && !LSTM && !PP), "narrow tile: 128 x 64 only");
+    static_assert(!NARROW || (MI == 1 && !LSTM), "narrow tile: 128 x 64 only");
     constexpr int TBM = NARROW ? 128 * MI : (MI ? 64 * MI : 32);    // tile rows (MI = 0: the 32-row tile, one row tile per wave)
     constexpr int BN = NARROW ? 64 : MBN;               // tile columns
     constexpr int NA = TBM / 32, NW = BN / 32;          // float4 staging loads per thread of A / of W
@@ -202,24 +164,21 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
     // of a K-tile is base + immediate; an XOR swizzle of the 16-byte chunks, the first version, cost three address VALU ops
     // per slice, and VALU time is matrix-pipe time on gfx950: tools/ubench/coissue.hip), every float4 16-byte aligned, and
     // the 192-row double buffer is 51 KB instead of 54 KB, so THREE workgroups fit the CU's 160 KB.
-    constexpr bool SKEW = MI <= 1 && !PP;
+    constexpr bool SKEW = MI <= 1;
     constexpr int RBLK = SKEW ? 544 : 16 * MLD_PAD;             // floats per block of 16 rows
     constexpr int A_FLOATS = (TBM / 16) * RBLK, BUF_FLOATS = ((TBM + BN) / 16) * RBLK;
     auto lds_off = [](int row, int k) {                         // float offset of (row, k) inside a tile
         return SKEW ? (row >> 4) * 544 + (row & 15) * 32 + 4 * ((row & 15) >> 1) + k : row * MLD_PAD + k;
     };
     // double-buffered tiles: [2][A | W] -> two (padded 128-row tiles) or three workgroups per CU
-    constexpr int NBUF = PP ? 1 : (LSTM ? VFR_LSTM_NBUF : VFR_GEMM_NBUF);
-    __shared__ __attribute__((aligned(16))) float lds_all[(PP ? 2 : 1) * NBUF * BUF_FLOATS];
+    __shared__ __attribute__((aligned(16))) float lds_all[2 * BUF_FLOATS];
+    float *lds = lds_all;                                // (a pointer, not the array's name: the register allocation of every kernel hangs on it)
     __shared__ int otab_s[CHALO ? TBM : 1];              // CHALO: padded output pixel of every tile row (pooled pixel under EPI_POOL2)
-    const int grp = PP ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;      // tile group of this wave
-    float *lds = lds_all + grp * NBUF * BUF_FLOATS;
-    const int tid = PP ? (int)(threadIdx.x & 255) : MULTI ? task_tid : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = MULTI ? task_tid : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = NARROW ? wave : wave >> 1, wn = NARROW ? 0 : wave & 1;
-    int64_t m0 = (int64_t)(PP ? blockIdx.x * 2 + grp : blockIdx.x) * TBM;
+    int64_t m0 = (int64_t)blockIdx.x * TBM;
     int n0 = blockIdx.y * BN;
     int by = blockIdx.y;                                 // column tile (LSTM step: 4 gates x 32 units)
-    bool active = true;                                  // PP: a group without a tile still takes part in the barriers
     if constexpr (MULTI) { by = task_by; m0 = task_m0; }
     else
     if (LSTM && g.xcd_cols > 0) {
@@ -235,16 +194,14 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
     if (!LSTM && g.xcd_cols > 0) {
         const unsigned L = blockIdx.x, per = 8u * (unsigned)g.xcd_cols, within = L % per;
         const int64_t rt = (int64_t)(L / per) * 8 + (within & 7u);
-        m0 = (PP ? rt * 2 + grp : rt) * TBM;
+        m0 = rt * TBM;
         n0 = (int)(within >> 3) * BN;
-        if (m0 >= g.M) { if (!PP) return; active = false; }     // grid padded to whole groups of 8 row tiles
+        if (m0 >= g.M) return;                           // grid padded to whole groups of 8 row tiles
     }
-    if (PP && !LSTM && m0 >= g.M) active = false;
     // LSTM step with a shrinking / growing active prefix: rows past the active count do nothing this step
     const int64_t Mrows = (LSTM && g.lstm_mcount) ? (int64_t)g.lstm_mcount[g.lstm_step] : g.M;
     const int64_t Mprev = (LSTM && g.lstm_mcount) ? (g.lstm_step > 0 ? (int64_t)g.lstm_mcount[g.lstm_step - 1] : 1) : Mrows;
-    if (LSTM && m0 >= Mrows) { if (!PP) return; active = false; }
-    if (!active) m0 = 0;                                 // keeps every clamped address below in range; nothing is stored
+    if (LSTM && m0 >= Mrows) return;
 
 #ifdef VFR_GEMM_STAMPS
     unsigned long long gst[4] = {0, 0, 0, 0}, gt0 = __builtin_amdgcn_s_memtime();
@@ -261,7 +218,7 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
     // count is wave-uniform and pinned to an SGPR (it derives from the wave index, a vector value).  A dead wave (TL == 0)
     // keeps its share of the staging loads / stores and every barrier.  GemmArgs::lstm_live bit 0 switches it on.
     constexpr std::integral_constant<int, TI> TIC{};
-    constexpr bool LIVE = LSTM && !PP && !TRAIN && NBUF == 2 && VFR_GEMM_PIPE;
+    constexpr bool LIVE = LSTM && !TRAIN;
     int tl = TI;
     if constexpr (LIVE) {
         if (g.lstm_live & 1) {
@@ -314,19 +271,14 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         }
     };
 
-    // staging registers: two sets in the software-pipelined loop (DEEP: K-tile kt + 2 is in flight in one set while kt + 3 is
-    // requested into the other -- 1 3/4 tiles of cover for the load latency instead of 3/4: it is what a 32-row tile, whose MFMA
-    // block is short, needs to keep enough bytes in flight), one set otherwise
-    constexpr bool DEEP = VFR_GEMM_DEEP && !PP && (LSTM ? VFR_LSTM_NBUF : VFR_GEMM_NBUF) == 2 && VFR_GEMM_PIPE;
-    constexpr std::integral_constant<int, 0> S0{};
-    constexpr std::integral_constant<int, 1> S1{};
-    float4 ra[DEEP ? 2 : 1][NA], rw[DEEP ? 2 : 1][NW];
+    // staging registers: K-tile kt + 2 is in flight in them while K-tile kt runs
+    float4 ra[NA], rw[NW];
     // Zero-fill of staged elements outside the operand (conv padding taps, the tail of a segmented K) is decided when the
     // load is ISSUED but applied (to the A side only) when the registers are written to LDS: a select right after the load
     // would make hipcc wait for the load (vmcnt(0)) before the MFMA block and expose its latency in every K-tile.
-    bool za[DEEP ? 2 : 1][NA];
+    bool za[NA];
 #pragma unroll
-    for (int i = 0; i < NA; ++i) { za[0][i] = false; za[DEEP ? 1 : 0][i] = false; }
+    for (int i = 0; i < NA; ++i) za[i] = false;
     // Staging loads.  Full K-tiles use UNCONDITIONAL loads (row index clamped into range; rows past M / N are
     // never stored) so the compiler can leave them in flight across the MFMA block -- a per-load bounds branch
     // makes hipcc drain vmcnt(0) right after issuing them.  Only the last, partial K-tile takes the guarded form.
@@ -365,8 +317,7 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         arow[i] = CONV ? g.A : g.A + ma * g.lda + kk;
         if (!LSTM && !CONV) aoff1[i] = (unsigned)(((ma - m0) * g.lda + kk) * 4);
     }
-    auto gload_full = [&](int k0, auto sc) {
-        constexpr int S = decltype(sc)::value;
+    auto gload_full = [&](int k0) {
         // aligned operands: uniform tile base (scalar registers) + the thread's fixed 32-bit offset inside the tile's rows
         // (at most 127 rows of lda floats: gemm_nt checks that this fits 32 bits) -- no vector address arithmetic per K-tile
         const char *ba = reinterpret_cast<const char *>(g.A + m0 * g.lda + k0);
@@ -376,27 +327,26 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             asm volatile("" : "+v"(aoff1[i]));
-            if (VEC) ra[S][i] = *reinterpret_cast<const float4 *>(ba + aoff1[i]);
-            else     ra[S][i] = make_float4(arow[i][k0], arow[i][k0 + 1], arow[i][k0 + 2], arow[i][k0 + 3]);
+            if (VEC) ra[i] = *reinterpret_cast<const float4 *>(ba + aoff1[i]);
+            else     ra[i] = make_float4(arow[i][k0], arow[i][k0 + 1], arow[i][k0 + 2], arow[i][k0 + 3]);
         }
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
             asm volatile("" : "+v"(woff1[i]));
-            if (VEC) rw[S][i] = *reinterpret_cast<const float4 *>(bw + woff1[i]);
-            else     rw[S][i] = make_float4(wrow[i][k0], wrow[i][k0 + 1], wrow[i][k0 + 2], wrow[i][k0 + 3]);
+            if (VEC) rw[i] = *reinterpret_cast<const float4 *>(bw + woff1[i]);
+            else     rw[i] = make_float4(wrow[i][k0], wrow[i][k0 + 1], wrow[i][k0 + 2], wrow[i][k0 + 3]);
         }
     };
-    auto gload_tail = [&](int k0, auto sc) {
-        constexpr int S = decltype(sc)::value;
+    auto gload_tail = [&](int k0) {
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int f = tid + 256 * i, row = f >> 3, kk = (f & 7) * 4;
-            ra[S][i] = load4_guard<false>(g.A, g.lda, m0 + row, g.M, k0 + kk, g.K);
+            ra[i] = load4_guard<false>(g.A, g.lda, m0 + row, g.M, k0 + kk, g.K);
         }
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
             const int f = tid + 256 * i, row = f >> 3, kk = (f & 7) * 4;
-            rw[S][i] = load4_guard<false>(g.W, g.ldw, (int64_t)n0 + row, g.N, k0 + kk, g.K);
+            rw[i] = load4_guard<false>(g.W, g.ldw, (int64_t)n0 + row, g.N, k0 + kk, g.K);
         }
     };
     // ---- implicit-GEMM conv loader: per staged row the output pixel is fixed, per K-tile the thread's 4 consecutive
@@ -482,8 +432,7 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         }
     }
     const int ctpt = CFAST ? g.conv_cin / MBK : 1;                      // K-tiles per tap
-    auto gload_conv_fast = [&](int k0, auto sc) {
-        constexpr int S = decltype(sc)::value;
+    auto gload_conv_fast = [&](int k0) {
         const int kt = k0 / MBK, tap = kt / ctpt, ci0 = (kt - tap * ctpt) * MBK;
         const int ky = (tap * 11) >> 5, kx = tap - 3 * ky;             // tap / 3 for tap < 9
         if constexpr (CHALO) {
@@ -491,9 +440,9 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
             const char *ba = reinterpret_cast<const char *>(g.A + ((chalo0 + dp) * g.conv_cin + ci0));
             const char *bw = reinterpret_cast<const char *>(g.W + (int64_t)n0 * g.ldw + k0);
 #pragma unroll
-            for (int i = 0; i < NA; ++i) { asm volatile("" : "+v"(coffb[i])); ra[S][i] = *reinterpret_cast<const float4 *>(ba + coffb[i]); }
+            for (int i = 0; i < NA; ++i) { asm volatile("" : "+v"(coffb[i])); ra[i] = *reinterpret_cast<const float4 *>(ba + coffb[i]); }
 #pragma unroll
-            for (int i = 0; i < NW; ++i) { asm volatile("" : "+v"(woff1[i])); rw[S][i] = *reinterpret_cast<const float4 *>(bw + woff1[i]); }
+            for (int i = 0; i < NW; ++i) { asm volatile("" : "+v"(woff1[i])); rw[i] = *reinterpret_cast<const float4 *>(bw + woff1[i]); }
             return;
         }
         const int dpix = (ky - 1) * g.conv_w + (kx - 1);
@@ -505,17 +454,16 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         for (int i = 0; i < NA; ++i) {
             const bool ok = (ctap[i] & tbit) != 0;
             // outside the image: the row's own pixel (always inside), zeroed when the registers go to LDS
-            ra[S][i] = *reinterpret_cast<const float4 *>(ba + (ok ? coffb[i] : coffb[i] - dbytes));
-            za[S][i] = !ok;
+            ra[i] = *reinterpret_cast<const float4 *>(ba + (ok ? coffb[i] : coffb[i] - dbytes));
+            za[i] = !ok;
         }
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
             asm volatile("" : "+v"(woff1[i]));
-            rw[S][i] = *reinterpret_cast<const float4 *>(bw + woff1[i]);
+            rw[i] = *reinterpret_cast<const float4 *>(bw + woff1[i]);
         }
     };
-    auto gload_conv = [&](int k0, auto sc) {
-        constexpr int S = decltype(sc)::value;
+    auto gload_conv = [&](int k0) {
         const int kk = (tid & 7) * 4, k = k0 + kk;
         const bool kok = k < g.K;
         const int kc = kok ? k : 0;
@@ -525,11 +473,11 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
             const int iy = coy[i] + ky - 1, ix = cox[i] + kx - 1;
             const bool ok = kok && crow_ok[i] && iy >= 0 && iy < g.conv_h && ix >= 0 && ix < g.conv_w;
             const int64_t off = ok ? (((int64_t)cn[i] * g.conv_h + iy) * g.conv_w + ix) * g.conv_cin + ci : 0;
-            ra[S][i] = *reinterpret_cast<const float4 *>(g.A + off);
-            za[S][i] = !ok;
+            ra[i] = *reinterpret_cast<const float4 *>(g.A + off);
+            za[i] = !ok;
         }
 #pragma unroll
-        for (int i = 0; i < NW; ++i) rw[S][i] = *reinterpret_cast<const float4 *>(wrow[i] - kk + kc);    // row clamped, k clamped
+        for (int i = 0; i < NW; ++i) rw[i] = *reinterpret_cast<const float4 *>(wrow[i] - kk + kc);    // row clamped, k clamped
     };
     // ---- segmented-K loader (LSTM step): tiles [0, nk1) walk [A | W] over K, tiles [nk1, nk1+nk2) walk [A2 | W2] over K2.
     // A partial last tile of a segment is shifted BACK to end exactly at the segment's end (nothing is read past a row);
@@ -539,8 +487,7 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
     bool zq = false;
     // MULTI: buffer resource over the h operand (raw buffer, 32-bit byte offsets: lstm_steps_pair checks the 4 GB bound)
     __amdgpu_buffer_rsrc_t hrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(MULTI ? g.A2 : nullptr), 0, MULTI ? 0xFFFFFFFFu : 0u, 0x00020000);
-    auto gload_seg = [&](int k0t, auto sc) {
-        constexpr int S = decltype(sc)::value;
+    auto gload_seg = [&](int k0t) {
         if constexpr (LFAST) {           // one segment of whole K-tiles: scalar base + the thread's fixed offsets, nothing to select
             const char *ba = reinterpret_cast<const char *>(g.A2 + k0t);
             const char *bw = reinterpret_cast<const char *>(g.W2 + k0t);
@@ -553,13 +500,13 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
                 for (int i = 0; i < NA; ++i) {
                     asm volatile("" : "+v"(aoff2[i]));
                     const vfr_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, (int)aoff2[i], k0t * 4, 16);
-                    ra[S][i] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+                    ra[i] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
                 }
             } else
 #pragma unroll
-            for (int i = 0; i < NA; ++i) { asm volatile("" : "+v"(aoff2[i])); ra[S][i] = *reinterpret_cast<const float4 *>(ba + aoff2[i]); }
+            for (int i = 0; i < NA; ++i) { asm volatile("" : "+v"(aoff2[i])); ra[i] = *reinterpret_cast<const float4 *>(ba + aoff2[i]); }
 #pragma unroll
-            for (int i = 0; i < NW; ++i) { asm volatile("" : "+v"(woff2[i])); rw[S][i] = *reinterpret_cast<const float4 *>(bw + woff2[i]); }
+            for (int i = 0; i < NW; ++i) { asm volatile("" : "+v"(woff2[i])); rw[i] = *reinterpret_cast<const float4 *>(bw + woff2[i]); }
             return;
         }
         const int kt = k0t / MBK;
@@ -572,17 +519,17 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         const char *bw = reinterpret_cast<const char *>((second ? g.W2 : g.W) + kb);
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
-            ra[S][i] = *reinterpret_cast<const float4 *>(ba + (second ? aoff2[i] : aoff1[i]));
-            za[S][i] = zq;
+            ra[i] = *reinterpret_cast<const float4 *>(ba + (second ? aoff2[i] : aoff1[i]));
+            za[i] = zq;
         }
 #pragma unroll
-        for (int i = 0; i < NW; ++i) rw[S][i] = *reinterpret_cast<const float4 *>(bw + (second ? woff2[i] : woff1[i]));
+        for (int i = 0; i < NW; ++i) rw[i] = *reinterpret_cast<const float4 *>(bw + (second ? woff2[i] : woff1[i]));
     };
     // LSTM step on the projection table (K == 0) with a short remainder of the recurrent segment (H = 1000: 31 K-tiles + 8):
     // the remainder does not get a K-tile of its own (a shifted-back tile is 24 zero products in 32 -- 2.3 % of the launch's
     // MFMAs); its <= 2 k-slices are fetched as MFMA fragments straight from global memory at the head of the kernel and run
     // after the last full tile -- the same k-ascending chain, bit for bit.
-    const int ktail = (LSTM && !PP && g.K == 0 && g.K2 > MBK && (g.K2 % MBK) != 0 && (g.K2 % MBK) <= 8) ? g.K2 % MBK : 0;
+    const int ktail = (LSTM && g.K == 0 && g.K2 > MBK && (g.K2 % MBK) != 0 && (g.K2 % MBK) <= 8) ? g.K2 % MBK : 0;
     constexpr int TI_ = MI ? 2 * MI : 1;
     float tfa[2][TI_], tfb[2][4];
     if (LSTM && ktail) {
@@ -625,46 +572,45 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
     };
     const int nk_full = LSTM ? nk1 + (ktail ? g.K2 / MBK : (g.K2 + MBK - 1) / MBK)
                              : CONV ? (g.K + MBK - 1) / MBK : g.K / MBK;     // conv / lstm: every tile through a select loader
-    auto swrite = [&](int b, auto sc) {
-        constexpr int S = decltype(sc)::value;
+    auto swrite = [&](int b) {
         float *As = lds + b * BUF_FLOATS, *Ws = As + A_FLOATS;
 #ifdef VFR_GEMM_NOSWRITE      /* TIMING EXPERIMENT ONLY (wrong results): staged registers are consumed but never written to LDS */
 #pragma unroll
-        for (int i = 0; i < NA; ++i) asm volatile("" :: "v"(ra[S][i].x), "v"(ra[S][i].y), "v"(ra[S][i].z), "v"(ra[S][i].w));
+        for (int i = 0; i < NA; ++i) asm volatile("" :: "v"(ra[i].x), "v"(ra[i].y), "v"(ra[i].z), "v"(ra[i].w));
 #pragma unroll
-        for (int i = 0; i < NW; ++i) asm volatile("" :: "v"(rw[S][i].x), "v"(rw[S][i].y), "v"(rw[S][i].z), "v"(rw[S][i].w));
+        for (int i = 0; i < NW; ++i) asm volatile("" :: "v"(rw[i].x), "v"(rw[i].y), "v"(rw[i].z), "v"(rw[i].w));
         return;
 #endif
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int f = tid + 256 * i, row = f >> 3, kk = (f & 7) * 4;
-            float4 v = ra[S][i];
-            if ((CONV && !CHALO) || (LSTM && !LFAST)) { const bool z = za[S][i]; v.x = z ? 0.f : v.x; v.y = z ? 0.f : v.y; v.z = z ? 0.f : v.z; v.w = z ? 0.f : v.w; }
+            float4 v = ra[i];
+            if ((CONV && !CHALO) || (LSTM && !LFAST)) { const bool z = za[i]; v.x = z ? 0.f : v.x; v.y = z ? 0.f : v.y; v.z = z ? 0.f : v.z; v.w = z ? 0.f : v.w; }
             *reinterpret_cast<float4 *>(&As[lds_off(row, kk)]) = v;
         }
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
             const int f = tid + 256 * i, row = f >> 3, kk = (f & 7) * 4;
-            float4 v = rw[S][i];
+            float4 v = rw[i];
             // (W is not zero-filled: wherever a k lies outside the operand the A side is zero, and the weight re-read from a
             // clamped address beside it is finite, so the product leaves the chain as it is)
             *reinterpret_cast<float4 *>(&Ws[lds_off(row, kk)]) = v;
         }
     };
     // one staged float4 (piece j < NA: of A, else of W) -> LDS: the pieces of swrite, for the interleaved schedule
-    auto swrite_piece = [&](int b, auto sc, int j) {
-        constexpr int S = decltype(sc)::value;
+    auto swrite_piece = [&](int b, int j) {
         float *As = lds + b * BUF_FLOATS, *Ws = As + A_FLOATS;
         if (j < NA) {
             const int f = tid + 256 * j, row = f >> 3, kk = (f & 7) * 4;
-            float4 v = ra[S][j];
-            if ((CONV && !CHALO) || (LSTM && !LFAST)) { const bool z = za[S][j]; v.x = z ? 0.f : v.x; v.y = z ? 0.f : v.y; v.z = z ? 0.f : v.z; v.w = z ? 0.f : v.w; }
+            float4 v = ra[j];
+            if ((CONV && !CHALO) || (LSTM && !LFAST)) { const bool z = za[j]; v.x = z ? 0.f : v.x; v.y = z ? 0.f : v.y; v.z = z ? 0.f : v.z; v.w = z ? 0.f : v.w; }
             *reinterpret_cast<float4 *>(&As[lds_off(row, kk)]) = v;
         } else {
             const int i = j - NA, f = tid + 256 * i, row = f >> 3, kk = (f & 7) * 4;
-            *reinterpret_cast<float4 *>(&Ws[lds_off(row, kk)]) = rw[S][i];
+            *reinterpret_cast<float4 *>(&Ws[lds_off(row, kk)]) = rw[i];
         }
     };
+    // one K-tile from LDS buffer b, on its own: the partial last tile of a dense GEMM
     auto compute = [&](int b) {
         const float *As = lds + b * BUF_FLOATS, *Ws = As + A_FLOATS;
         // fragment of tile row block ti at k-slice k4: ONE dword per lane, A[16*ti + (lane & 15)][4*k4 + (lane >> 4)] -- exactly
@@ -675,8 +621,8 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         // fragment ring: the reads of slice k4+DEPTH are issued (and pinned) BEFORE the MFMAs of slice k4, so their
         // latency hides under the matrix pipe.  DEPTH 2 matters when a workgroup is ALONE on its CU (partial last round, small
         // launches): with one slice of cover a lone wave's stream stalled on LDS latency and a half-filled round cost as much
-        // as a full one; with two it costs half.  The LSTM step (64-row tiles, always several rounds) is 1.5 % faster with 1.
-        constexpr int DEPTH = LSTM ? VFR_LSTM_DEPTH : 2, RING = DEPTH + 1;
+        // as a full one; with two it costs half.
+        constexpr int DEPTH = 2, RING = DEPTH + 1;
         float fa[RING][TI], fb[RING][4];
 #pragma unroll
         for (int d = 0; d < DEPTH; ++d) {
@@ -705,9 +651,6 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         }
     };
 
-    // main loop over the FULL K-tiles, branch-free: iteration kt prefetches tile min(kt+1, last) (the final
-    // iteration re-reads its own tile, which is harmless) so no control-flow join sits between the loads and the
-    // MFMA block -- a join there makes the compiler drain vmcnt(0) before the first MFMA.
     // Fused LSTM step: what the gate epilogue needs from memory -- the previous cell state of the lane's 4*TI cells and the four
     // bias pairs of its unit -- is requested at the HEAD of the tile, beside the projection-table gather (one latency window,
     // 12 registers held across the K-loop at 64 rows), not at the head of the epilogue, where nothing else of this wave is in
@@ -733,13 +676,12 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
                 }
         }
     };
-    constexpr bool CELL_EARLY = LSTM && !PP && NBUF == 2 && VFR_GEMM_PIPE && VFR_LSTM_CELL_EARLY;
-    auto gload_main = [&](int k0, auto sc) { if (LSTM) gload_seg(k0, sc); else if (CFAST) gload_conv_fast(k0, sc); else if (CONV) gload_conv(k0, sc); else gload_full(k0, sc); };
+    auto gload_main = [&](int k0) { if (LSTM) gload_seg(k0); else if (CFAST) gload_conv_fast(k0); else if (CONV) gload_conv(k0); else gload_full(k0); };
     // Fused LSTM step, dispatched form: the gate epilogue of the wave's first TL row blocks (the live ones)
     auto lstm_epilogue = [&](auto TLC) {
         constexpr int TL = decltype(TLC)::value;
-        // (gemm_lstm_epilogue.inc takes from this scope: TL, TLC; TI, TRAIN, MULTI, CELL_EARLY; g, by, m0, Mrows, wm, wn, l15, lq,
-        // acc, cprev, bi, bf, bg, bo, load_cell_inputs -- and declares H, unit, valid, cnew, hnew, gsave)
+        // (gemm_lstm_epilogue.inc takes from this scope: TL; TI, TRAIN, MULTI; g, by, m0, Mrows, wm, wn, l15, lq,
+        // acc, cprev, bi, bf, bg, bo -- and declares H, unit, valid, cnew, hnew, gsave)
         if constexpr (LSTM && TL > 0) {
 #include "gemm_lstm_epilogue.inc"
         }
@@ -752,24 +694,7 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         // The counter is read by tests only; no output is computed from it.
         if constexpr (LIVE) { if (g.lstm_blocks && lane == 0 && TL > 0) atomicAdd(g.lstm_blocks, (unsigned)TL); }
     };
-    if (PP) {
-        // group g runs  C0 L1 C1 L2 ... C(nk-1)  delayed by g phases;  Ck = MFMA block on K-tile k (LDS), Lk = K-tile k from
-        // registers to LDS + issue the loads of K-tile k+1.  One workgroup barrier per phase.
-        const int nk = nk_full;
-        init_acc(TIC);
-        if (active && nk > 0) { gload_main(0, S0); swrite(0, S0); if (nk > 1) gload_main(MBK, S0); }
-        __syncthreads();
-        GSTAMP(0)
-        for (int p = 0; p < 2 * nk; ++p) {
-            const int q = p - grp;
-            if (active && q >= 0 && q < 2 * nk - 1) {
-                const int k = q >> 1;
-                if (q & 1) { swrite(0, S0); if (k + 2 < nk) gload_main((k + 2) * MBK, S0); }
-                else compute(0);
-            }
-            __syncthreads();
-        }
-    } else if (NBUF == 2 && VFR_GEMM_PIPE) {
+    {   // (a scope: the loop's text declares names the epilogue's text declares again)
         // K-tile loop, software-pipelined so that NOTHING but the barrier itself sits between two MFMA blocks.  Per K-tile kt
         // (8 k-slices of 4, TI*4 MFMAs each):
         //   slice 1   registers (K-tile kt+1, loaded during the previous tile) -> the other LDS buffer: it was last read for
@@ -778,14 +703,14 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
         //             make hipcc drain vmcnt before the MFMAs)
         //   slice 8-DEPTH  barrier (K-tile kt+1 visible), then the fragment reads continue seamlessly into K-tile kt+1
         // so the LDS writes, the load issue and the first fragment reads of the next tile all run under MFMAs of this one.
-        constexpr int DEPTH = LSTM ? VFR_LSTM_DEPTH : 2, RING = DEPTH == 1 ? 2 : 4, NS = MBK / 4;
+        constexpr int DEPTH = LSTM ? LSTM_DEPTH : 2, RING = DEPTH == 1 ? 2 : 4, NS = MBK / 4;
         const int nk = nk_full;
         // TL = row blocks of this wave that are computed: TI, or the live count of an LSTM tile's wave (see LIVE above).  With
         // TL == 0 the wave only stages: its loads, its LDS stores (as one block at slice 1) and the barriers.
         if constexpr (LIVE) {
-            // (gemm_pipe_loop.inc takes from this scope: TL, TLC; TI, NA, NW, RBLK, BUF_FLOATS, A_FLOATS, DEPTH, RING, NS, DEEP,
-            // CELL_EARLY, the kernel's template flags; nk, lds, lds_off, wm, wn, l15, lq, acc; S0, S1; gload_main, swrite,
-            // swrite_piece, init_acc, load_cell_inputs -- and declares fa, fb, frag_read, ktile, kt)
+            // (gemm_pipe_loop.inc takes from this scope: TL, TLC; TI, NA, NW, RBLK, BUF_FLOATS, A_FLOATS, DEPTH, RING, NS, the
+            // kernel's template flags; nk, lds, lds_off, wm, wn, l15, lq, acc; gload_main, swrite, swrite_piece, init_acc,
+            // load_cell_inputs -- and declares fa, fb, frag_read, ktile, kt)
             auto pipe = [&](auto TLC) {
                 constexpr int TL = decltype(TLC)::value;
 #include "gemm_pipe_loop.inc"
@@ -809,46 +734,17 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
 #include "gemm_pipe_loop.inc"
         if (!CONV && !LSTM && (g.K % MBK)) {   // partial last tile: guarded loads, zero padded (fma(0,0,acc) == acc)
             __syncthreads();
-            gload_tail(nk_full * MBK, S0);
-            swrite(0, S0);
+            gload_tail(nk_full * MBK);
+            swrite(0);
             __syncthreads();
             compute(0);
         }
-    } else {
-    init_acc(TIC);
-    if (nk_full > 0) { gload_main(0, S0); swrite(0, S0); }
-    __syncthreads();
-    GSTAMP(0)
-    for (int kt = 0; kt < nk_full; ++kt) {
-        const int nxt = kt + 1 < nk_full ? kt + 1 : nk_full - 1;
-        gload_main(nxt * MBK, S0);
-        __builtin_amdgcn_sched_barrier(0);     // keep the prefetch ahead of the MFMA block (hipcc sinks it otherwise)
-        if (VFR_GEMM_SETPRIO) __builtin_amdgcn_s_setprio(1);
-        compute(kt % NBUF);
-        if (VFR_GEMM_SETPRIO) __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        // the other buffer was last read in iteration kt-1 and every wave has passed that iteration's barrier:
-        // refill it now (overlapping the other waves' MFMAs); one barrier per K-tile
-        if (NBUF == 1) __syncthreads();     // single buffer: everyone must finish reading before the refill
-        swrite((kt + 1) % NBUF, S0);
-#ifndef VFR_GEMM_NOSYNC
-        __syncthreads();
-#endif
     }
-    if (!CONV && !LSTM && (g.K % MBK)) {   // partial last tile: guarded loads, zero padded (fma(0,0,acc) == acc)
-        gload_tail(nk_full * MBK, S0);
-        swrite(nk_full % NBUF, S0);
-        __syncthreads();
-        compute(nk_full % NBUF);
-    }
-    }
-    if (PP && !active) return;
     tail_mfma(TIC);
 
     GSTAMP(1)
     if (LSTM) {
         constexpr int TL = TI;
-        constexpr std::integral_constant<int, TL> TLC{};
 #include "gemm_lstm_epilogue.inc"
         GSTAMP(2)
 #ifdef VFR_GEMM_STAMPS
@@ -882,13 +778,13 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
     // K (ResNet's expansion convolutions: K = 64 .. 512, an output and a residual of 4x the input each) then runs at ~1 TB/s on
     // its epilogue alone.  The tile is parked in the (now idle) staging buffers and leaves as whole rows, 16 bytes per lane:
     // same values, same order of the additions.
-    if constexpr (!LSTM && !CHALO && !PP) {
+    if constexpr (!LSTM && !CHALO) {
         const bool res = (g.epi & EPI_RES) != 0;
         const bool vec_epi = !(g.epi & (EPI_POOL2 | EPI_VIS)) && ((g.N | (int)g.ldo | (res ? (int)g.ldr : 0)) & 3) == 0 &&
                              ((((uintptr_t)g.out) | (res ? (uintptr_t)g.res : (uintptr_t)0)) & 15) == 0;
         if (vec_epi) {
             constexpr int CLD = BN + 4, C4 = BN / 4;                      // padded row stride (floats); float4 per tile row
-            static_assert(TBM * CLD <= NBUF * BUF_FLOATS, "the output tile must fit the staging buffers");
+            static_assert(TBM * CLD <= 2 * BUF_FLOATS, "the output tile must fit the staging buffers");
             __syncthreads();                                             // every wave has read its last fragments
             float *ct = lds;
 #pragma unroll
@@ -966,10 +862,10 @@ __device__ __forceinline__ void gemm_nt_mfma_body(const GemmArgs &g, int task_by
 }
 
 template <bool VEC, int MI = 2>
-__global__ __launch_bounds__(256, (VFR_GEMM_NBUF == 1 || MI <= 1) ? 3 : 2) void gemm_nt_mfma(GemmArgs g) { gemm_nt_mfma_body<VEC, false, false, MI>(g); }
+__global__ __launch_bounds__(256, MI <= 1 ? 3 : 2) void gemm_nt_mfma(GemmArgs g) { gemm_nt_mfma_body<VEC, false, false, MI>(g); }
 
 // dense operands with N <= 64 (ResNet's stem and layer1 1x1 convolutions): 128 x 64 tiles, no MFMA spent on absent columns
-__global__ __launch_bounds__(256, 3) void gemm_nt_mfma_narrow(GemmArgs g) { gemm_nt_mfma_body<true, false, false, 1, false, true>(g); }
+__global__ __launch_bounds__(256, 3) void gemm_nt_mfma_narrow(GemmArgs g) { gemm_nt_mfma_body<true, false, false, 1, true>(g); }
 
 template <bool VEC>
 __global__ __launch_bounds__(256, 2) void gemm_nt_mfma_pair(GemmPair gp)
@@ -979,13 +875,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_mfma_pair(GemmPair gp)
 }
 
 template <int MI = 2, bool NARROW = false, bool CFAST = false, bool CHALO = false>
-__global__ __launch_bounds__(256, MI <= 1 ? 3 : 2) void conv3x3_nhwc_mfma(GemmArgs g) { gemm_nt_mfma_body<true, true, false, MI, false, NARROW, false, CFAST, false, CHALO>(g); }
+__global__ __launch_bounds__(256, MI <= 1 ? 3 : 2) void conv3x3_nhwc_mfma(GemmArgs g) { gemm_nt_mfma_body<true, true, false, MI, NARROW, false, CFAST, false, CHALO>(g); }
 
 template <int MI, bool LFAST = false>
-__global__ __launch_bounds__(256, MI <= 1 ? 3 : VFR_LSTM_WAVES) void lstm_step_mfma_pair(GemmPair gp)
+__global__ __launch_bounds__(256, MI <= 1 ? 3 : 2) void lstm_step_mfma_pair(GemmPair gp)
 {
     const GemmArgs g = gp.p[blockIdx.z];      // private copy, see gemm_nt_mfma_pair
-    gemm_nt_mfma_body<true, false, true, MI, false, false, false, false, LFAST>(g);
+    gemm_nt_mfma_body<true, false, true, MI, false, false, false, LFAST>(g);
 }
 // ---- all T steps of both directions in ONE launch ------------------------------------------------------------------------
 // One launch per time step ends every step with a partial round of workgroups (3.3 .. 6.6 rounds of the chip's 768 slots per
@@ -1120,7 +1016,7 @@ __global__ __launch_bounds__(256, MI <= 1 ? 3 : 2) void lstm_steps_mfma_kernel(L
             // task loop and held in registers across it -- 40 more VGPRs than the per-step kernel, spilled at three workgroups per CU)
             int tid_task = tid;
             asm volatile("" : "+v"(tid_task));
-            gemm_nt_mfma_body<true, false, true, MI, false, false, false, false, true, false, true>(g, by, (int64_t)rt * TBM, tid_task);
+            gemm_nt_mfma_body<true, false, true, MI, false, false, false, true, false, true>(g, by, (int64_t)rt * TBM, tid_task);
         }
         SSTAMP(2)
         // The next ticket is drawn only now (a ticket drawn before the task would sit idle for the task's whole duration, and the
@@ -1181,7 +1077,7 @@ template <int MI>
 __global__ __launch_bounds__(256, MI <= 1 ? 3 : 2) void lstm_step_train_mfma_pair(GemmPair gp)
 {
     const GemmArgs g = gp.p[blockIdx.z];
-    gemm_nt_mfma_body<true, false, true, MI, false, false, true>(g);
+    gemm_nt_mfma_body<true, false, true, MI, false, true>(g);
 }
 // blockIdx.z = problem * nsplit + K range: 32-row tiles over one K range of one problem (gemm_nt_splitk_pair)
 __global__ __launch_bounds__(256, 3) void gemm_nt_mfma_splitk_pair(GemmPair gp, int nsplit, int64_t out_stride)
@@ -1192,13 +1088,6 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_mfma_splitk_pair(GemmPair gp, 
     g.A += (int64_t)j * kc; g.W += (int64_t)j * kc; g.out += (int64_t)j * out_stride; g.K = kc;
     gemm_nt_mfma_body<true, false, false, 0>(g);
 }
-__global__ __launch_bounds__(512, 2) void lstm_step_mfma_pair_pp(GemmPair gp)
-{
-    const GemmArgs g = gp.p[blockIdx.z];
-    gemm_nt_mfma_body<true, false, true, 2, true>(g);
-}
-template <bool VEC>
-__global__ __launch_bounds__(512, 2) void gemm_nt_mfma_pp(GemmArgs g) { gemm_nt_mfma_body<VEC, false, false, 2, true>(g); }
 
 __global__ __launch_bounds__(256) void repack_rows_kernel(const float *__restrict__ src, int64_t ld_src, int rows, int cols,
                                                           float *__restrict__ dst)
@@ -1246,6 +1135,15 @@ static bool gemm_vec_ok(const GemmArgs &g)
     return ((g.lda | g.ldw) & 3) == 0 && ((((uintptr_t)g.A) | ((uintptr_t)g.W)) & 15) == 0;
 }
 
+// Tile height of the per-step launch for R GEMM rows, in lstm_tile numbering (1 = 64 rows, 2 = 128, 3 = 32).
+// 64-row tiles by default: a step is only a few rounds of the chip's 512 workgroup slots, a partial last round of
+// 128-row tiles costs as much as a full one (a workgroup alone on a CU is not twice as fast), and half-size tiles halve that
+// loss -- measured faster at every batch size from 625 to 5000 queries (lstm_tile = 2 forces 128 rows).  Below ~700
+// rows (a rank's share of the batch on 8 GPUs) the step is hardly more than one round and 32-row tiles at three
+// workgroups per CU balance the CUs better still (tools/lstm_tile_sweep.py: -1 % at 625 rows, -11 % at 313; alone the
+// encoder also gains 1-2 % at 1250 / 2500 rows, but beside the clip encoder on the other stream it does not; +5 % at 5000).
+static int lstm_step_tile(int64_t R) { return opt_lstm_tile() ? opt_lstm_tile() : (R <= 700 ? 3 : 1); }
+
 int lstm_step_pair(const GemmArgs &g0, const GemmArgs &g1, hipStream_t st)
 {
     if (g0.M == 0) return VFR_OK;
@@ -1264,15 +1162,9 @@ int lstm_step_pair(const GemmArgs &g0, const GemmArgs &g1, hipStream_t st)
     }
     ProfScope prof(g0.site, st);
     GemmPair gp{{g0, g1}};
-    // 64-row tiles by default: a step is only a few rounds of the chip's 512 workgroup slots, a partial last round of
-    // 128-row tiles costs as much as a full one (a workgroup alone on a CU is not twice as fast), and half-size tiles halve that
-    // loss -- measured faster at every batch size from 625 to 5000 queries (lstm_tile = 2 forces 128 rows).  Below ~700
-    // rows (a rank's share of the batch on 8 GPUs) the step is hardly more than one round and 32-row tiles at three
-    // workgroups per CU balance the CUs better still (tools/lstm_tile_sweep.py: -1 % at 625 rows, -11 % at 313; alone the
-    // encoder also gains 1-2 % at 1250 / 2500 rows, but beside the clip encoder on the other stream it does not; +5 % at 5000).
-    const int tile = opt_lstm_tile() ? opt_lstm_tile() : (g0.M <= 700 ? 3 : 1);       // (= lstm_plan's tile for the per-step form)
+    const int tile = lstm_step_tile(g0.M);
     const int ncol = (int)cdiv(g0.lstm_H, 32), cpx = (int)cdiv(ncol, 8);
-    const bool xcd = opt_lstm_xcd() && !(tile == 2 && opt_gemm_pp());
+    const bool xcd = opt_lstm_xcd();
     if (xcd) gp.p[0].xcd_cols = gp.p[1].xcd_cols = cpx;
     gp.p[0].lstm_live = gp.p[1].lstm_live = opt_lstm_live_blocks() & 1;
     auto grid_for = [&](int rows) {
@@ -1285,7 +1177,7 @@ int lstm_step_pair(const GemmArgs &g0, const GemmArgs &g1, hipStream_t st)
         const int rem = g.K2 % MBK;
         return g.lstm_tok && g.K == 0 && g.K2 >= MBK && (rem == 0 || (g.K2 > MBK && rem <= 8));
     };
-    const bool lfast = opt_lstm_fast() && fast_ok(g0) && fast_ok(g1) && VFR_GEMM_PIPE && VFR_LSTM_NBUF == 2;
+    const bool lfast = opt_lstm_fast() && fast_ok(g0) && fast_ok(g1);
     if (g0.lstm_gates) {                     // training forward: the same step, gates stored as well (32- or 64-row tiles)
         VFR_REQUIRE(g1.lstm_gates, VFR_EINVAL, "lstm_step_pair: gates buffer for one direction only");
         if (tile == 3) hipLaunchKernelGGL(lstm_step_train_mfma_pair<0>, grid_for(32), dim3(256), 0, st, gp);
@@ -1296,9 +1188,6 @@ int lstm_step_pair(const GemmArgs &g0, const GemmArgs &g1, hipStream_t st)
     } else if (tile != 2) {
         if (lfast) hipLaunchKernelGGL((lstm_step_mfma_pair<1, true>), grid_for(64), dim3(256), 0, st, gp);
         else       hipLaunchKernelGGL(lstm_step_mfma_pair<1>, grid_for(64), dim3(256), 0, st, gp);
-    } else if (opt_gemm_pp()) {
-        dim3 grid((unsigned)cdiv(cdiv(g0.M, MBM), 2), (unsigned)cdiv(g0.lstm_H, 32), 2);
-        hipLaunchKernelGGL(lstm_step_mfma_pair_pp, grid, dim3(512), 0, st, gp);
     } else {
         hipLaunchKernelGGL(lstm_step_mfma_pair<2>, grid_for(MBM), dim3(256), 0, st, gp);
     }
@@ -1331,9 +1220,9 @@ LstmPlan lstm_plan(int64_t R, int H, int T, int cus)
     LstmPlan p{};
     const int rem = H % MBK, multi = opt_lstm_multi(), forced = opt_lstm_tile();
     const bool wanted = multi == 1 || (multi == 2 && forced == 0 && R >= opt_lstm_multi_min() && H >= 512);
-    p.one_launch = wanted && opt_lstm_fast() && opt_lstm_skip0() && opt_lstm_xcd() && bool(VFR_GEMM_PIPE) && VFR_LSTM_NBUF == 2 &&
+    p.one_launch = wanted && opt_lstm_fast() && opt_lstm_skip0() && opt_lstm_xcd() &&
                    (H % 4) == 0 && H >= MBK && H <= 1024 && (rem == 0 || (H > MBK && rem <= 8)) && ((R + 1) * 2 * (int64_t)H + MBK) * 4 < (1ll << 32);
-    p.tile = forced ? forced : (R <= 700 ? 3 : 1);               // 32-row tiles for small batches (lstm_step_pair)
+    p.tile = lstm_step_tile(R);
     if (p.one_launch) {
         if (multi == 2) p.tile = 2;
         else if (p.tile != 2 && p.tile != 3) p.tile = 1;
@@ -1499,24 +1388,32 @@ int gemm_nt(const GemmArgs &g, hipStream_t st)
         // wrap over window rows -- under 2 * 128 + 4 * w pixels)
         const bool cf = (g.conv_cin % MBK) == 0 && (int64_t)(g.conv_w + 1 + 2 * MBM + 4 * g.conv_w + 2 * g.conv_w + 2) * g.conv_cin * 4 < (1ll << 31);
         VFR_REQUIRE(!g.conv_halo || (cf && !(g.epi & EPI_RES)), VFR_EINVAL, "gemm_nt(conv): halo-padded activations need C_in %% 32 == 0 (and no residual)");
-#define VFR_CONV(MI_, NARROW_, GRID_, ARGS_)                                                                            \
-        do {                                                                                                            \
-            if (g.conv_halo) hipLaunchKernelGGL((conv3x3_nhwc_mfma<MI_, NARROW_, true, true>), GRID_, dim3(256), 0, st, ARGS_); \
-            else if (cf) hipLaunchKernelGGL((conv3x3_nhwc_mfma<MI_, NARROW_, true>), GRID_, dim3(256), 0, st, ARGS_);    \
-            else    hipLaunchKernelGGL((conv3x3_nhwc_mfma<MI_, NARROW_, false>), GRID_, dim3(256), 0, st, ARGS_);        \
-        } while (0)
+        // the loader: halo-padded activations, C_in a multiple of 32 (scalar taps), or the general one
+        auto kernel_for = [&](auto mi, auto narrow) -> void (*)(GemmArgs) {
+            constexpr int MI = decltype(mi)::value;
+            constexpr bool NARROW = decltype(narrow)::value;
+            return g.conv_halo ? conv3x3_nhwc_mfma<MI, NARROW, true, true> : cf ? conv3x3_nhwc_mfma<MI, NARROW, true> : conv3x3_nhwc_mfma<MI, NARROW, false>;
+        };
+        constexpr std::integral_constant<int, 1> MI1{};
+        constexpr std::integral_constant<int, 2> MI2{};
+        GemmArgs gx = g;
+        gx.xcd_cols = 0;
+        void (*kernel)(GemmArgs) = nullptr;
+        dim3 gr = grid;
         if (g.N <= 64) {                                      // conv1_x: 128 x 64 tiles, no MFMA spent on absent columns
-            VFR_CONV(1, true, dim3(grid.x, 1), g);
+            kernel = kernel_for(MI1, std::true_type{});
+            gr = dim3(grid.x, 1);
         } else if ((int64_t)grid.x * grid.y < 384) {          // under 1.5 workgroups per CU: 64-row tiles (as the dense GEMM)
-            VFR_CONV(1, false, dim3((unsigned)cdiv(g.M, 64), grid.y), g);
-        } else if (grid.y > 1 && grid.y <= 16 && grid.x >= 64) {     // XCD-aware tile order (see xcd_cols): activations stream once
-            GemmArgs gx = g;
-            gx.xcd_cols = (int)grid.y;
-            VFR_CONV(2, false, dim3((unsigned)(cdiv(grid.x, 8) * 8 * grid.y)), gx);
+            kernel = kernel_for(MI1, std::false_type{});
+            gr = dim3((unsigned)cdiv(g.M, 64), grid.y);
         } else {
-            VFR_CONV(2, false, grid, g);
+            kernel = kernel_for(MI2, std::false_type{});
+            if (grid.y > 1 && grid.y <= 16 && grid.x >= 64) {     // XCD-aware tile order (see xcd_cols): activations stream once
+                gx.xcd_cols = (int)grid.y;
+                gr = dim3((unsigned)(cdiv(grid.x, 8) * 8 * grid.y));
+            }
         }
-#undef VFR_CONV
+        hipLaunchKernelGGL(kernel, gr, dim3(256), 0, st, gx);
         VFR_CHECK_LAUNCH("conv3x3_nhwc_mfma");
         return VFR_OK;
     }
@@ -1526,73 +1423,44 @@ int gemm_nt(const GemmArgs &g, hipStream_t st)
         VFR_CHECK_LAUNCH("gemm_nt_valu");
         return VFR_OK;
     }
+    // ---- the dense MFMA forms: choose tile rows, grid and tile order once, then one launch per kernel ----
     const bool vec = gemm_vec_ok(g);
-    if (opt_gemm_small() != 64 && (int64_t)grid.x * grid.y < (opt_gemm_small() > 64 ? opt_gemm_small() : 384)) {
+    const int small = opt_gemm_small();
+    const int64_t tiles128 = (int64_t)grid.x * grid.y;
+    int rows;                                  // tile rows: 32, 64 or 128
+    bool large = false;                        // a large grid: XCD-aware tile order where the shape suits it
+    if (small != 64 && tiles128 < (small > 64 ? small : 384)) {
         // fewer 128-row workgroups than 1.5 per CU (context rows, output / query projections, VGG fc6-fc7): 32-row tiles at
         // three workgroups per CU -- four times the workgroups, so the CUs are evenly loaded (tools/small_gemm.py: 10-40 %
         // faster than 64-row tiles on every such GEMM of the pass; alone also 5 % at 824 tiles, a rank's clip encoder on 8 GPUs,
         // but not beside the query encoder on the other stream; slower from ~1600 tiles on.  "gemm_small" 64 forces the 64-row
         // tiles, a value above 64 moves the threshold)
-        dim3 grid32((unsigned)cdiv(g.M, 32), grid.y);
-        if (vec) hipLaunchKernelGGL((gemm_nt_mfma<true, 0>), grid32, dim3(256), 0, st, g);
-        else     hipLaunchKernelGGL((gemm_nt_mfma<false, 0>), grid32, dim3(256), 0, st, g);
-        VFR_CHECK_LAUNCH("gemm_nt_mfma<32>");
-        return VFR_OK;
-    }
-    if ((int64_t)grid.x * grid.y < 384) {
-        // (cross-check build of the same class: 64-row tiles)
-        dim3 grid64((unsigned)cdiv(g.M, 64), grid.y);
-        if (vec) hipLaunchKernelGGL((gemm_nt_mfma<true, 1>), grid64, dim3(256), 0, st, g);
-        else     hipLaunchKernelGGL((gemm_nt_mfma<false, 1>), grid64, dim3(256), 0, st, g);
-        VFR_CHECK_LAUNCH("gemm_nt_mfma<64>");
-        return VFR_OK;
-    }
-    if (vec && g.N <= 64) {
+        rows = 32;
+    } else if (tiles128 < 384) {
+        rows = 64;                             // (cross-check build of the same class: 64-row tiles)
+    } else if (vec && g.N <= 64) {
+        // 128 x 64 tiles, no MFMA spent on absent columns
         hipLaunchKernelGGL(gemm_nt_mfma_narrow, dim3(grid.x, 1), dim3(256), 0, st, g);
         VFR_CHECK_LAUNCH("gemm_nt_mfma_narrow");
         return VFR_OK;
+    } else {
+        // Short chains (K <= 2048: ResNet's 1x1 convolutions, the clip encoder's output layer): a 128-row tile's prologue and
+        // epilogue weigh as much as its few K-tiles, and three 64-row workgroups per CU cover them better than two 128-row ones
+        // (tools/resnet_layers.py: the expansion convolutions 179 -> 148 us, the whole ResNet-152 stack 33.9 -> 31.6 ms).  Long
+        // chains (the clip encoder's K = 4096) keep the 128-row tiles (123-127 TF against 117-120).
+        rows = (small == 1 || (small == 0 && g.K <= 2048)) ? 64 : MBM;
+        large = true;
     }
-    const bool pp = opt_gemm_pp() && (g.K % MBK) == 0 && g.K >= 2 * MBK;
-    // Short chains (K <= 2048: ResNet's 1x1 convolutions, the clip encoder's output layer): a 128-row tile's prologue and
-    // epilogue weigh as much as its few K-tiles, and three 64-row workgroups per CU cover them better than two 128-row ones
-    // (tools/resnet_layers.py: the expansion convolutions 179 -> 148 us, the whole ResNet-152 stack 33.9 -> 31.6 ms).  Long
-    // chains (the clip encoder's K = 4096) keep the 128-row tiles (123-127 TF against 117-120).
-    if (opt_gemm_small() == 1 || (opt_gemm_small() == 0 && g.K <= 2048)) {
-        const unsigned gx64 = (unsigned)cdiv(g.M, 64);
-        GemmArgs gx = g;
-        const bool xcd = grid.y > 1 && grid.y <= 16 && gx64 >= 64;
-        gx.xcd_cols = xcd ? (int)grid.y : 0;
-        dim3 gr = xcd ? dim3((unsigned)(cdiv(gx64, 8) * 8 * grid.y)) : dim3(gx64, grid.y);
-        if (vec) hipLaunchKernelGGL((gemm_nt_mfma<true, 1>), gr, dim3(256), 0, st, gx);
-        else     hipLaunchKernelGGL((gemm_nt_mfma<false, 1>), gr, dim3(256), 0, st, gx);
-        VFR_CHECK_LAUNCH("gemm_nt_mfma<64>(large)");
-        return VFR_OK;
-    }
-    if (grid.y > 1 && grid.y <= 16 && grid.x >= 64) {
-        // tall GEMM with a few column tiles (the clip encoder's seg x W1: 1641 x 4): XCD-aware tile order, see xcd_cols
-        GemmArgs gx = g;
-        gx.xcd_cols = (int)grid.y;
-        if (pp) {
-            dim3 grid1((unsigned)(cdiv(cdiv(grid.x, 2), 8) * 8 * grid.y));
-            if (vec) hipLaunchKernelGGL(gemm_nt_mfma_pp<true>, grid1, dim3(512), 0, st, gx);
-            else     hipLaunchKernelGGL(gemm_nt_mfma_pp<false>, grid1, dim3(512), 0, st, gx);
-        } else {
-            dim3 grid1((unsigned)(cdiv(grid.x, 8) * 8 * grid.y));
-            if (vec) hipLaunchKernelGGL(gemm_nt_mfma<true>, grid1, dim3(256), 0, st, gx);
-            else     hipLaunchKernelGGL(gemm_nt_mfma<false>, grid1, dim3(256), 0, st, gx);
-        }
-        VFR_CHECK_LAUNCH("gemm_nt_mfma(xcd)");
-        return VFR_OK;
-    }
-    if (pp) {
-        dim3 grid2((unsigned)cdiv(grid.x, 2), grid.y);
-        if (vec) hipLaunchKernelGGL(gemm_nt_mfma_pp<true>, grid2, dim3(512), 0, st, g);
-        else     hipLaunchKernelGGL(gemm_nt_mfma_pp<false>, grid2, dim3(512), 0, st, g);
-        VFR_CHECK_LAUNCH("gemm_nt_mfma_pp");
-        return VFR_OK;
-    }
-    if (vec) hipLaunchKernelGGL(gemm_nt_mfma<true>, grid, dim3(256), 0, st, g);
-    else     hipLaunchKernelGGL(gemm_nt_mfma<false>, grid, dim3(256), 0, st, g);
+    const unsigned rt = (unsigned)cdiv(g.M, rows);
+    // tall GEMM with a few column tiles (the clip encoder's seg x W1: 1641 x 4): XCD-aware tile order, see xcd_cols
+    const bool xcd = large && grid.y > 1 && grid.y <= 16 && rt >= 64;
+    GemmArgs gx = g;
+    gx.xcd_cols = xcd ? (int)grid.y : 0;
+    const dim3 gr = xcd ? dim3((unsigned)(cdiv(rt, 8) * 8 * grid.y)) : dim3(rt, grid.y);
+    void (*const kernel)(GemmArgs) = rows == 32 ? (vec ? gemm_nt_mfma<true, 0> : gemm_nt_mfma<false, 0>)
+                                   : rows == 64 ? (vec ? gemm_nt_mfma<true, 1> : gemm_nt_mfma<false, 1>)
+                                                : (vec ? gemm_nt_mfma<true, 2> : gemm_nt_mfma<false, 2>);
+    hipLaunchKernelGGL(kernel, gr, dim3(256), 0, st, gx);
     VFR_CHECK_LAUNCH("gemm_nt_mfma");
     return VFR_OK;
 }

@@ -1,12 +1,12 @@
 // The gate epilogue of the fused LSTM step in gemm_nt_mfma_body (gemm.hip), as TEXT: included there once in place (TL = TI) and
 // once inside the closure the inference step dispatches on its live block count -- see gemm_pipe_loop.inc for why.  Expects
-// TL / TLC beside the names of the enclosing function; finishes the cells of the wave's first TL row blocks.
+// TL beside the names of the enclosing function; finishes the cells of the wave's first TL row blocks.
         // tile columns are (gate, unit): a lane holds i, f, g, o of unit 32*blockIdx.y + 16*wn + (lane & 15) in its four column
         // tiles, for 4*TI rows -- every cell is finished by ONE lane, no exchange
         const int H = g.lstm_H, unit = by * 32 + wn * 16 + l15;
         const bool valid = unit < H;
-        if constexpr (!CELL_EARLY) load_cell_inputs(TLC);
-        // batched and branch-free: the previous-cell loads first (clamped addresses), then 4*TI independent gate evaluations
+        // batched and branch-free: the previous cell state and the biases were requested at the head of the tile
+        // (load_cell_inputs), here 4*TI independent gate evaluations
         // in ONE basic block (the asm pins the results ahead of the predicated stores; hipcc otherwise sinks each cell's ~190
         // instructions into its own store predicate, one serial dependency chain after the other)
         float cnew[TL][4], hnew[TL][4];

@@ -17,9 +17,10 @@
         };
         // the first K-tile's loads are in flight while the accumulators are initialised (C-in / the LSTM table gather: two
         // dependent load rounds whose latency would otherwise stand alone at the head of every tile)
-        if (nk > 0) gload_main(0, S0);
+        if (nk > 0) gload_main(0);
         init_acc(TLC);
-        if constexpr (CELL_EARLY) load_cell_inputs(TLC);
+        // (fused LSTM step: the gate epilogue's loads ride in the same latency window; nothing in the other kernels)
+        load_cell_inputs(TLC);
         // Accumulators that start from LOADED values (C-in, the LSTM projection-table gather) must have landed before the loop is
         // entered: otherwise the waitcnt pass, merging the loop-entry state into the loop header, guards the first MFMAs of EVERY
         // trip with vmcnt(3) .. vmcnt(0) -- which on the back edge drains the staging loads requested five slices earlier, i.e. the
@@ -28,13 +29,8 @@
         // (unconditional: behind a run-time test the wait would itself sit on one arm of a join)
         __builtin_amdgcn_s_waitcnt(0x0F70);                                                    // vmcnt(0)
         if (nk > 0) {
-            swrite(0, S0);
-            if constexpr (DEEP) {        // K-tile 1 into set 1, K-tile 2 into set 0 (free again): two tiles in flight from here on
-                gload_main((nk > 1 ? 1 : 0) * MBK, S1);
-                gload_main((nk > 2 ? 2 : nk - 1) * MBK, S0);
-            } else {
-                gload_main((nk > 1 ? 1 : 0) * MBK, S0);
-            }
+            swrite(0);
+            gload_main((nk > 1 ? 1 : 0) * MBK);
         }
         __syncthreads();
         GSTAMP(0)
@@ -55,12 +51,12 @@
                 if (sn < NS) frag_read(cb, sn, sn % RING);
                 else         frag_read(nb, sn - NS, sn % RING);    // (past the last K-tile: stale data, never used)
                 __builtin_amdgcn_sched_barrier(0);
-                // VFR_GEMM_SPREAD: the staging stores of K-tile kt + 1 go out ONE behind each MFMA of slices 1 and 2 instead of as a
+                // SPREAD: the staging stores of K-tile kt + 1 go out ONE behind each MFMA of slices 1 and 2 instead of as a
                 // block behind slice 1 (a wave alone on its SIMD issues no MFMA while it moves 5-8 float4 to the LDS: 254 cycles
                 // per K-tile of a 32-row tile)
                 constexpr int NM = TL * 4, NPIECE = NA + NW;
-                static_assert(!VFR_GEMM_SPREAD || TL < TI || NPIECE <= 2 * NM, "staging pieces must fit behind the MFMAs of two slices");
-                constexpr bool SPREAD = VFR_GEMM_SPREAD && NPIECE <= 2 * NM;      // (too few live MFMAs to hang the pieces on: one block)
+                static_assert(TL < TI || NPIECE <= 2 * NM, "staging pieces must fit behind the MFMAs of two slices");
+                constexpr bool SPREAD = NPIECE <= 2 * NM;      // (too few live MFMAs to hang the pieces on: one block)
 #pragma unroll
                 for (int ti = 0; ti < TL; ++ti)
 #pragma unroll
@@ -68,10 +64,9 @@
                         acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[k4 % RING][ti], fb[k4 % RING][tj], acc[ti][tj], 0, 0, 0);
                         if (SPREAD && (k4 == 1 || k4 == 2)) {
                             const int piece = (k4 - 1) * NM + ti * 4 + tj;
-                            if (piece < NPIECE) swrite_piece(nb, std::integral_constant<int, DEEP ? nb : 0>{}, piece);
+                            if (piece < NPIECE) swrite_piece(nb, piece);
                         }
                     }
-#if VFR_GEMM_SPREAD == 2
                 // (pin the order: MFMA, [the piece's zero-selects], its LDS store -- left alone the scheduler hangs four of the stores
                 // behind the first MFMA)
                 if (SPREAD && (k4 == 1 || k4 == 2)) {
@@ -85,16 +80,9 @@
                         }
                     }
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
-                // DEEP: K-tile kt + 1 sits in register set nb (= its parity); once it is in LDS that set takes K-tile kt + 3,
-                // while set cb still holds K-tile kt + 2 in flight
-                if (!SPREAD && k4 == 1) swrite(nb, std::integral_constant<int, DEEP ? nb : 0>{});
-                if (k4 == VFR_GLOAD_SLICE) {
-                    const int ahead = DEEP ? 3 : 2;
-                    const int t2 = kt + ahead < nk ? kt + ahead : nk - 1;
-                    gload_main(t2 * MBK, std::integral_constant<int, DEEP ? nb : 0>{});
-                }
+                if (!SPREAD && k4 == 1) swrite(nb);
+                if (k4 == GLOAD_SLICE) gload_main((kt + 2 < nk ? kt + 2 : nk - 1) * MBK);
             }
         };
         int kt = 0;

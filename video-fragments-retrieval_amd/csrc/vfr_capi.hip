@@ -20,7 +20,6 @@ static std::atomic<int> g_opt_lstm_skip0{1};       // 1: the first LSTM step ski
 static std::atomic<int> g_opt_score_tasks{0};      // > 0: wave-tasks the scorer's plan aims for (experiment; 0 = automatic)
 static std::atomic<int> g_opt_score_smallq{64};    // batches of up to this many queries (<= 64) are scored with lanes = clips / videos (vfr_score_topk_mfma, f32); 0: never
 static std::atomic<int> g_opt_score_pre_b{0};      // > 0: videos in ladder stage B (experiment; 0 = Nv/16 capped at 640)
-static std::atomic<int> g_opt_gemm_pp{0};          // 1: ping-pong schedule (512-thread workgroups, two tile groups) for the large MFMA GEMMs (experiment)
 static std::atomic<int> g_opt_mfma_min{128};        // banks of fewer videos go to the exact scorer (the pre-filter's fixed launches cost more); tests set 0
 static std::atomic<int> g_opt_lstm_small{2};       // batches of up to this many queries (<= 4) take the vector-chain LSTM step (measured: 17 / 25 / 38 us per step at 1 / 2 / 4 queries against 34 for the MFMA tiles); 0: always the tiles
 static std::atomic<int> g_opt_lstm_persist{1};     // 1: one or two queries run the whole sequence in ONE launch with the weights resident in LDS (lstm_seq_small_kernel); 0: one launch per step
@@ -29,7 +28,6 @@ static std::atomic<int> g_opt_vgg_direct1{1};      // 1: the first VGG convoluti
 static std::atomic<int> g_opt_smallq_select{1};    // 1: the few-queries path takes its top-k by video selection (smallq_select_kernel); 0: key array + selection tree (cross-check)
 static std::atomic<int> g_opt_lstm_persist_min{2}; // batches ABOVE this many queries (up to 32, the model's shape) take the single-launch MFMA sequence kernel; 32: never
 static std::atomic<int> g_opt_lstm_persist_fault{-1}; // TEST HOOK: workgroup of the single-launch sequence kernels that withholds its h of step 1 (-1: none)
-static std::atomic<int> g_opt_lstm_persist_max{32}; // ... and up to this many.  33 .. 64 are possible (two parts of <= 32 queries taking turns on the same resident weights): bit-identical, but 0.70 ms per 64-query pass against 0.62 for the tile steps (the two-part kernel's 275 weight registers + two parts' state spill): off by default
 static std::atomic<int> g_opt_lstm_multi{2};       // all T steps of the fused BiLSTM in ONE launch (gemm.hip: lstm_steps_mfma_kernel) -- same bits as one launch per step.  2 (default): automatic -- from lstm_multi_min rows on, at H >= 512, with 128-row tiles (where it measured faster: HISTORY.md round 17; below ~2 000 rows the hand-overs between dependent tasks cost more than kernel boundaries) and only while lstm_tile is 0; 1: always (tile height by lstm_tile); 0: never
 static std::atomic<int> g_opt_lstm_multi_min{2500}; // lstm_multi 2: GEMM rows (queries + 1) from which the one-launch form is taken
 static std::atomic<int> g_opt_lstm_live_blocks{1}; // fused LSTM step, bit 0 (default on): a wave issues matrix work and gate epilogue only for its live 16-row blocks (rows below the active count, units below H) -- same bits; 0: every block of the tile (cross-check).  Bit 1 (tests): count the issued blocks in the workspace (vfr_bilstm_debug_offset)
@@ -49,7 +47,7 @@ struct Opt { const char *name; std::atomic<int> *v; };
 static const Opt g_opts[] = {
     {"gemm", &g_opt_gemm}, {"profile", &g_opt_profile}, {"score_fast", &g_opt_score_fast}, {"score_split", &g_opt_score_split},
     {"score_pre_b", &g_opt_score_pre_b}, {"score_smallq", &g_opt_score_smallq}, {"score_tasks", &g_opt_score_tasks}, {"lstm_skip0", &g_opt_lstm_skip0},
-    {"lstm_xcd", &g_opt_lstm_xcd}, {"gemm_small", &g_opt_gemm_small}, {"lstm_tile", &g_opt_lstm_tile}, {"lstm_small4", &g_opt_lstm_small4}, {"lstm_persist", &g_opt_lstm_persist}, {"lstm_persist_min", &g_opt_lstm_persist_min}, {"lstm_fast", &g_opt_lstm_fast}, {"lstm_multi", &g_opt_lstm_multi}, {"lstm_multi_min", &g_opt_lstm_multi_min}, {"lstm_multi_taken", &g_opt_lstm_multi_taken}, {"lstm_live_blocks", &g_opt_lstm_live_blocks}, {"lstm_persist_max", &g_opt_lstm_persist_max}, {"lstm_persist_fault", &g_opt_lstm_persist_fault}, {"vgg_fuse_pool", &g_opt_vgg_fuse_pool}, {"vgg_direct1", &g_opt_vgg_direct1}, {"vgg_halo", &g_opt_vgg_halo}, {"score_kth_seed", &g_opt_kth_seed}, {"score_smallq_rank", &g_opt_smallq_rank}, {"score_smallq_select", &g_opt_smallq_select}, {"gemm_pp", &g_opt_gemm_pp}, {"score_mfma_min", &g_opt_mfma_min}, {"lstm_small", &g_opt_lstm_small}, {"score_defer", &g_opt_score_defer}, {"score_sort", &g_opt_score_sort}, {"score_hist", &g_opt_score_hist}, {"score_i8", &g_opt_score_i8},
+    {"lstm_xcd", &g_opt_lstm_xcd}, {"gemm_small", &g_opt_gemm_small}, {"lstm_tile", &g_opt_lstm_tile}, {"lstm_small4", &g_opt_lstm_small4}, {"lstm_persist", &g_opt_lstm_persist}, {"lstm_persist_min", &g_opt_lstm_persist_min}, {"lstm_fast", &g_opt_lstm_fast}, {"lstm_multi", &g_opt_lstm_multi}, {"lstm_multi_min", &g_opt_lstm_multi_min}, {"lstm_multi_taken", &g_opt_lstm_multi_taken}, {"lstm_live_blocks", &g_opt_lstm_live_blocks}, {"lstm_persist_fault", &g_opt_lstm_persist_fault}, {"vgg_fuse_pool", &g_opt_vgg_fuse_pool}, {"vgg_direct1", &g_opt_vgg_direct1}, {"vgg_halo", &g_opt_vgg_halo}, {"score_kth_seed", &g_opt_kth_seed}, {"score_smallq_rank", &g_opt_smallq_rank}, {"score_smallq_select", &g_opt_smallq_select}, {"score_mfma_min", &g_opt_mfma_min}, {"lstm_small", &g_opt_lstm_small}, {"score_defer", &g_opt_score_defer}, {"score_sort", &g_opt_score_sort}, {"score_hist", &g_opt_score_hist}, {"score_i8", &g_opt_score_i8},
 };
 
 struct ProfPair { int site; hipEvent_t a, b; int units; };      // units: launches' worth of work the bracket stands for
@@ -113,7 +111,6 @@ int opt_lstm_multi() { return g_opt_lstm_multi; }
 int opt_lstm_multi_min() { return g_opt_lstm_multi_min; }
 int opt_lstm_live_blocks() { return g_opt_lstm_live_blocks; }
 void note_lstm_multi_taken(int how) { g_opt_lstm_multi_taken = how; }
-int opt_lstm_persist_max() { return g_opt_lstm_persist_max; }
 int opt_lstm_persist_fault() { return g_opt_lstm_persist_fault; }
 int opt_vgg_fuse_pool() { return g_opt_vgg_fuse_pool; }
 int opt_vgg_direct1() { return g_opt_vgg_direct1; }
@@ -135,7 +132,6 @@ int device_cu_count()
 static std::atomic<unsigned *> g_fault_word{nullptr};
 unsigned *fault_word() { return g_fault_word.load(); }
 int opt_lstm_small() { return g_opt_lstm_small; }
-int opt_gemm_pp() { return g_opt_gemm_pp; }
 int opt_mfma_min() { return g_opt_mfma_min; }
 int opt_score_defer() { return g_opt_score_defer; }
 int opt_score_sort() { return g_opt_score_sort; }

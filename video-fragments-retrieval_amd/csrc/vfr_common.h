@@ -35,7 +35,6 @@ int opt_lstm_multi_min();
 int opt_lstm_live_blocks();
 void note_lstm_multi_taken(int how);   // read-only option "lstm_multi_taken" (vfr_capi.hip): which way the last vfr_bilstm_final_f32 went
 int opt_lstm_persist_min();
-int opt_lstm_persist_max();
 int opt_lstm_persist_fault();
 int opt_vgg_fuse_pool();
 int opt_vgg_direct1();
@@ -46,7 +45,6 @@ int device_cu_count();                  // of the CURRENT device (cached per dev
 constexpr int VFR_MAX_DEVICES = 64;     // per-device caches (CU count, kernel attributes)
 unsigned *fault_word();                 // vfr_set_fault_word: device-accessible host word kernels raise fault bits in (nullable)
 int opt_lstm_small();
-int opt_gemm_pp();
 int opt_mfma_min();
 int opt_score_defer();
 int opt_score_sort();
