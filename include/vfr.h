@@ -539,6 +539,44 @@ int vfr_score_prior_f32(const float *Q, int64_t Nq, const float *V, const int32_
                         float *out_dist, int64_t *out_idx, int num_rank, const float *rank_dist, const int64_t *rank_idx,
                         int64_t *count_lt, const int32_t *table_off, const float *table, int *bad, void *workspace,
                         size_t workspace_bytes, vfr_stream_t stream);
+/* ---- windowed retrieval for long videos: the candidate set is every window of at most max_len clips, whatever the length of a
+ * video -- the proposal set long-video corpora (Charades-STA, ActivityNet Captions, TACoS) are searched over.  Every other scoring
+ * entry point puts one whole video on a lane and refuses max_clips > 64; this one scans the FLAT clip axis (lane = start clip, a
+ * running sum over the next max_len end clips), so nothing in it is sized by a video.
+ *   candidates  every moment (video v, start s, end e) with 0 <= s <= e < n_v and e - s + 1 <= max_len, 1 <= max_len <= 64.
+ *   score   the canonical chain, BIT-IDENTICAL to what vfr_score_moments_f32 writes (k-ascending fp32 fma chain of ((v - q) + eps)^2,
+ *           IEEE sqrt, sequential fp32 sum s -> e, one IEEE division by (float)(e - s + 1)).
+ *   keys    (fp32 bits of the score << 32) | (id_base + moment_offsets[v] + j), j = the moment's position in utils.generate_moments(n_v)
+ *           order: the ids stay canonical, so max_len >= max_clips gives vfr_score_topk_f32 (VFR_SCORE_EXACT) BIT FOR BIT and every
+ *           decoder of ids still works.  Ascending, padding (+inf, -1).
+ * vfr_score_window_f32: out_dist / out_idx [Nq,k] = the k smallest candidate keys; count_lt[r][q] += the candidates that sort
+ *   strictly before (rank_dist[r][q], rank_idx[r][q]).  num_rank <= 4, counts are ADDED (shards chain; lists merge with
+ *   vfr_topk_merge_f32); k = 0 with counts only is allowed.  Nq = 0: nothing is written.  Nv = 0 or total_clips = 0: the lists are
+ *   padding, the counts stay.  Videos without clips own no candidate.
+ * vfr_score_window_span_keys_f32: items int32 [Np, 4] = (query row, corpus-global video, start, end) -> out_keys[p] = the key of that
+ *   span (what a rank key of a ground-truth span is, without an own-video row of n^2 entries).  An item whose video lies outside
+ *   [vid_base, vid_base + Nv) is left untouched: pre-fill VFR_KEY_EMPTY and reduce MIN over the shards.  A malformed item (query row
+ *   outside [0, Nq), start < 0, end < start, end >= n_v, end - start + 1 > 64) sets *bad (nullable, device int) and is left untouched.
+ * Limits: 1 <= max_len <= 64, k <= 448, id_base + total moments <= 2^32 (bounded as total_clips (max_clips + 1) / 2), Nq * k < 2^31,
+ * any D (D = 100 with 16-byte aligned Q and V takes the fast path of the scan), and max_clips <= 1024: the longest video the CPU
+ * oracle (vfo_score_moments) can check -- the kernels keep nothing that is sized by a video (their int32 moment positions would hold
+ * up to 32 767 clips).  VFR_EINVAL before
+ * anything is enqueued for the bad host-side arguments, a workspace shorter than vfr_score_window_workspace_bytes among them.  Exact
+ * arithmetic only (no MFMA pre-filter), stride 1.
+ * LDS of a vfr_score_window_f32 wave, in bytes: 416 (the query row; fast path only) + 512 (the clip distances of a tile of 64 flat
+ * clips and its halo of max_len - 1) + 8 slots(k) (the key list: 128 / 256 / 512 slots for k <= 64 / 192 / 448): at most 5 024,
+ * whatever the clip counts are.
+ * vfr_score_window_workspace_bytes = 256 + 8 k Nq C, C = min(ceil(4096 / Nq), ceil(total_clips / 64), 256) >= 1 = the bound on the
+ * chunks the flat clip axis is cut into: O(Nq k) (0 for a bad argument).                                                       */
+size_t vfr_score_window_workspace_bytes(int64_t Nq, int total_clips, int k);
+int vfr_score_window_f32(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets, const int64_t *moment_offsets, int Nv,
+                         int total_clips, int max_clips, int D, float eps, int64_t id_base, int max_len, int k, float *out_dist,
+                         int64_t *out_idx, int num_rank, const float *rank_dist, const int64_t *rank_idx, int64_t *count_lt,
+                         void *workspace, size_t workspace_bytes, vfr_stream_t stream);
+int vfr_score_window_span_keys_f32(const float *Q, int64_t Nq, const float *V, const int32_t *clip_offsets,
+                                   const int64_t *moment_offsets, int Nv, int total_clips, int D, float eps, int64_t id_base,
+                                   int64_t vid_base, const int32_t *items, int64_t Np, int64_t *out_keys, int *bad,
+                                   vfr_stream_t stream);
 /* Device self-check of the arithmetic model the pre-filter's margins and the MFMA GEMMs' bit-exactness assume: a
  * v_mfma_f32_16x16x4_f32 = four fp32 fmas, k ascending, on its accumulator (denormals kept).  A, B [16, K] device rows
  * (K % 4 == 0; make them adversarial: wide exponent range, cancellation, denormals): C = A B^T by the matrix pipe against an

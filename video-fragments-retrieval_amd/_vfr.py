@@ -91,6 +91,10 @@ SIGNATURES = {
     "vfr_score_prior_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "vfr_score_prior_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _i32, _vp, _vp, _i32,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vfr_score_window_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "vfr_score_window_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp,
+                                    _vp, _vp, _sz, _vp]),
+    "vfr_score_window_span_keys_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "vfr_mfma_selfcheck": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "vfr_mfma_selfcheck_i8": (_i32, [_vp, _vp, _i32, _vp, _vp]),
     "vfr_score_i8_debug": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _f32, _vp, ctypes.c_size_t] + [_vp] * 11),
@@ -873,6 +877,62 @@ def score_prior(Q: torch.Tensor, bank: VideoBank, table, k: int, level: str = "m
                                      _ptr(rank_idx), _ptr(count_lt), off.data_ptr(), val.data_ptr(), _ptr(bad), workspace.data_ptr(),
                                      nbytes, _stream()), "vfr_score_prior_f32")
     return od, oi, count_lt
+
+
+WINDOW_MAX_LEN = 64                           # include/vfr.h: 1 <= max_len <= 64
+
+
+def score_window(Q: torch.Tensor, bank: VideoBank, max_len: int, k: int, rank_dist=None, rank_idx=None, count_lt=None,
+                 workspace: torch.Tensor | None = None, eps: float = 1e-6):
+    """Windowed retrieval (include/vfr.h vfr_score_window_f32): the candidates are the moments of at most ``max_len`` clips
+    (1 .. 64), in videos of any length up to 1 024 clips; scores and ids are the canonical ones, so ``max_len >= bank.max_clips``
+    gives ``score_topk(mode="exact")``.  The k best candidates, padded with (+inf, -1).  rank_dist / rank_idx [R, Nq] (or [Nq]),
+    R <= 4: ``count_lt`` [R, Nq] int64 += the candidates that sort before each rank key (allocated zeroed when None).
+    Returns (dist [Nq,k] | None, idx [Nq,k] int64 | None, count_lt | None)."""
+    Q = _dev(Q, torch.float32, "Q")
+    if Q.dim() != 2 or Q.shape[1] != bank.dim:
+        raise ValueError(f"score_window: Q must be [Nq, {bank.dim}], got {tuple(Q.shape)}")
+    if bank.emb.device != Q.device:
+        raise ValueError(f"score_window: the bank lives on {bank.emb.device}, the queries on {Q.device}")
+    Nq, dev = Q.shape[0], Q.device
+    od, oi = _out_lists(Nq, k, dev)
+    rank_dist, rank_idx, count_lt, R = _rank_keys(rank_dist, rank_idx, count_lt, Nq, dev)
+    nbytes = lib().vfr_score_window_workspace_bytes(Nq, bank.total_clips, k)
+    workspace = _workspace(workspace, nbytes, dev)
+    workspace._vfr_bank = None                   # whatever a pre-filter left in this workspace is overwritten
+    _check(lib().vfr_score_window_f32(Q.data_ptr(), Nq, bank.emb.data_ptr(), bank.clip_off.data_ptr(), bank.mom_off.data_ptr(),
+                                      bank.num_videos, bank.total_clips, bank.max_clips, bank.dim, eps, bank.id_base, int(max_len), k,
+                                      _ptr(od), _ptr(oi), R, _ptr(rank_dist), _ptr(rank_idx), _ptr(count_lt), workspace.data_ptr(),
+                                      nbytes, _stream()), "vfr_score_window_f32")
+    return od, oi, count_lt
+
+
+def window_span_keys(Q: torch.Tensor, bank: VideoBank, items: torch.Tensor, vid_base: int = 0, out: torch.Tensor | None = None,
+                     bad: torch.Tensor | None = None, eps: float = 1e-6) -> torch.Tensor:
+    """Keys of named spans (include/vfr.h vfr_score_window_span_keys_f32): ``items`` int32 [Np, 4] = (query row, corpus-global
+    video, start, end), spans of at most 64 clips -> int64 [Np] packed (score, canonical moment id) keys.  Items whose video is
+    outside [vid_base, vid_base + Nv) and malformed items are left untouched (``out`` is KEY_EMPTY pre-filled when None); ``bad``
+    (int32 [1], optional) is set to 1 by a malformed item."""
+    Q = _dev(Q, torch.float32, "Q")
+    items = _dev(items, torch.int32, "items")
+    if Q.dim() != 2 or Q.shape[1] != bank.dim:
+        raise ValueError(f"window_span_keys: Q must be [Nq, {bank.dim}], got {tuple(Q.shape)}")
+    if items.dim() != 2 or items.shape[1] != 4:
+        raise ValueError(f"window_span_keys: items must be int32 [Np, 4], got {tuple(items.shape)}")
+    if bank.emb.device != Q.device or items.device != Q.device:
+        raise ValueError(f"window_span_keys: the bank lives on {bank.emb.device}, the items on {items.device}, the queries on {Q.device}")
+    Np = items.shape[0]
+    if out is None:
+        out = torch.full((Np,), KEY_EMPTY, dtype=torch.int64, device=Q.device)
+    elif out.numel() != Np or not out.is_contiguous():
+        raise ValueError(f"window_span_keys: out must be contiguous int64 [{Np}]")
+    out = _dev(out, torch.int64, "out")
+    _check(lib().vfr_score_window_span_keys_f32(Q.data_ptr(), Q.shape[0], bank.emb.data_ptr(), bank.clip_off.data_ptr(),
+                                                bank.mom_off.data_ptr(), bank.num_videos, bank.total_clips, bank.dim, eps,
+                                                bank.id_base, int(vid_base), items.data_ptr() if Np else 0,
+                                                Np, out.data_ptr() if Np else 0, _ptr(bad), _stream()),
+           "vfr_score_window_span_keys_f32")
+    return out
 
 
 FUSION_MAX_SWEEP = 16                         # include/vfr.h VFR_FUSION_MAX_SWEEP

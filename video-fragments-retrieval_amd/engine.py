@@ -109,6 +109,12 @@ class HipOps:
     def score_prior_own(self, Q, bank, table, own_local, bad=None):
         return self.v.score_prior_own(Q, bank, table, own_local, bad=bad)
 
+    def score_window(self, Q, bank, max_len, k, rank_dist=None, rank_idx=None, count_lt=None, workspace=None):
+        return self.v.score_window(Q, bank, max_len, k, rank_dist, rank_idx, count_lt=count_lt, workspace=workspace)
+
+    def window_span_keys(self, Q, bank, items, vid_base=0, out=None, bad=None):
+        return self.v.window_span_keys(Q, bank, items, vid_base, out, bad=bad)
+
     def slice_bank(self, bank, counts, v0, v1):
         return self.v.slice_bank(bank, counts, v0, v1)
 
@@ -1186,6 +1192,140 @@ def corpus_prior_topk(shard: CorpusShard, Q, table: MomentTable, k, level="momen
     return od, oi, vid, cnt, unreachable
 
 
+WINDOW_MAX_LEN = 64                           # include/vfr.h: 1 <= max_len <= 64
+WINDOW_MAX_CLIPS = 1024                       # include/vfr.h: the longest video the CPU oracle can check
+
+
+def _check_window(max_len, who):
+    if not 1 <= int(max_len) <= WINDOW_MAX_LEN:
+        raise ValueError(f"{who}: max_len = {max_len} (1 .. {WINDOW_MAX_LEN})")
+    return int(max_len)
+
+
+def window_positives(times, counts_own, thresholds, max_len, strict=True, agree=2):
+    """The ground-truth-positive WINDOWS of a query batch, per threshold: ``out[r]`` = int32 [P_r, 3] rows (query row, start, end)
+    of every window of at most ``max_len`` clips of the query's own video (``counts_own[q]`` clips, any number of them) that at
+    least ``agree`` annotators of ``times[q]`` overlap with IoU > ``thresholds[r]`` (>= when not ``strict``) -- the label rule of
+    ``gt_label_table`` (float64 ``intersection / union`` like ``utils.get_iou``), stated on windows instead of on a row of all
+    n (n + 1) / 2 moments.  Rows are ordered by query, then start, then end.  Host numpy, vectorised over the queries of one clip
+    count; for a video of at most 64 clips and ``max_len >= n`` the rows are exactly the moments ``gt_label_table`` labels 1."""
+    L = _check_window(max_len, "window_positives")
+    counts_own = np.asarray(counts_own, np.int64).reshape(-1)
+    t, na = times if isinstance(times, tuple) else pack_times(times)
+    if len(na) != len(counts_own):
+        raise ValueError(f"window_positives: {len(na)} annotations with {len(counts_own)} clip counts")
+    found = [[] for _ in thresholds]
+    A = t.shape[1] if len(na) else 0
+    valid = np.arange(A)[None, :, None] < na[:, None, None] if len(na) else None          # [Nq, A, 1]
+    for n in np.unique(counts_own):
+        n = int(n)
+        if n <= 0:
+            continue
+        s = np.repeat(np.arange(n, dtype=np.int64), L)
+        e = s + np.tile(np.arange(L, dtype=np.int64), n)
+        keep = e < n
+        s, e = s[keep], e[keep]                                                       # (start, end) ascending
+        qs = np.nonzero(counts_own == n)[0]
+        step = max(1, (1 << 22) // max(1, A * len(s)))                                # queries per block: ~32 MB of float64 IoUs
+        for b in range(0, len(qs), step):
+            q = qs[b:b + step]
+            ts, te = t[q, :, 0:1].astype(np.int64), t[q, :, 1:2].astype(np.int64)     # [nq, A, 1]
+            inter = np.maximum(np.minimum(te, e) + 1 - np.maximum(ts, s), 0)
+            union = np.maximum(te, e) + 1 - np.minimum(ts, s)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                iou = inter / union                                                   # [nq, A, M] float64
+            for r, thr in enumerate(thresholds):
+                hit = ((iou > thr) if strict else (iou >= thr)) & valid[q]
+                qi, mi = np.nonzero(hit.sum(axis=1) >= agree)
+                found[r].append(np.stack([q[qi], s[mi], e[mi]], axis=1))
+    out = []
+    for rows in found:
+        rows = np.concatenate(rows) if rows else np.zeros((0, 3), np.int64)
+        out.append(np.ascontiguousarray(rows[np.lexsort((rows[:, 2], rows[:, 1], rows[:, 0]))], dtype=np.int32))
+    return out
+
+
+def decode_moments(shard: CorpusShard, ids):
+    """Global moment ids (any shape, int64; < 0 = padding) -> (video, start, end) int64 tensors of that shape, -1 at the padding:
+    the video by ``searchsorted`` on the corpus's moment offsets, the span by the closed-form inverse of the position in
+    ``generate_moments(n)`` order (singles first, then per start the ends after it) -- no table of a video's moments is built."""
+    ids = torch.as_tensor(ids, dtype=torch.int64)
+    dev = ids.device
+    mom = torch.from_numpy(np.asarray(shard.mom_off_all, np.int64)).to(dev)
+    cnt = torch.from_numpy(np.asarray(shard.counts_all, np.int64)).to(dev)
+    ok = (ids >= 0) & (ids < int(shard.mom_off_all[-1]))
+    if not len(shard.counts_all):
+        none = torch.full_like(ids, -1)
+        return none, none.clone(), none.clone()
+    safe = torch.where(ok, ids, torch.zeros_like(ids))
+    vid = (torch.searchsorted(mom, safe, right=True) - 1).clamp(0, len(shard.counts_all) - 1)
+    n = cnt[vid]
+    j = safe - mom[vid]
+    # j >= n: x = j - n lies in the row of start s, which begins at R(s) = s (2 n - s - 1) / 2: s = the largest start with R(s) <= x
+    x = (j - n).clamp(min=0)
+    b = 2 * n - 1
+    s = ((b.double() - torch.sqrt((b * b - 8 * x).clamp(min=0).double())) / 2).floor().long().clamp(min=0)
+    row = lambda u: (u * (2 * n - u - 1)) // 2
+    s = torch.where(row(s) > x, s - 1, s)                                             # (the square root rounded the wrong way)
+    s = torch.where(row(s + 1) <= x, s + 1, s)
+    e = s + 1 + (x - row(s))
+    single = j < n
+    s, e = torch.where(single, j, s), torch.where(single, j, e)
+    none = torch.full_like(ids, -1)
+    return torch.where(ok, vid, none), torch.where(ok, s, none), torch.where(ok, e, none)
+
+
+def corpus_window_topk(shard: CorpusShard, Q, max_len, k, own_global=None, positives=None, ops=None, world=1, workspace=None):
+    """Windowed retrieval over the corpus: the candidates are the moments of at most ``max_len`` clips (1 .. 64) in videos of any
+    length up to 1 024 clips -- the sliding-window proposal set of the long-video corpora; scores and ids are the canonical ones
+    (``decode_moments`` gives the spans).  A moment never spans shards, so the lists merge with the moment-key merge and the counts
+    add.  This path is chosen by the caller: nothing switches between it and ``corpus_topk`` / ``corpus_prior_topk`` by itself.
+    Ground truth: ``own_global`` [Nq] and ``positives`` = per threshold (at most 4) the rows (query row, start, end) of the positive
+    windows of the query's own video (``window_positives``; rows longer than ``max_len`` are no candidates and are dropped) ->
+    ranks [R, Nq] = 0-based position of the best positive window in the (score, id) order of the candidates.  A query without a
+    positive window does not raise: its rank is the number of candidates in the corpus -- no k finds it -- and it is marked in
+    ``unreachable`` (bool [R, Nq]).  A row that does not lie inside its video raises ValueError.
+    Returns (dist [Nq,k], moment id [Nq,k] int64, video index [Nq,k] int64 (-1 = padding), ranks | None, unreachable | None);
+    lists are None for k = 0."""
+    ops = ops or HipOps()
+    L = _check_window(max_len, "corpus_window_topk")
+    nmax = int(shard.counts_all.max()) if len(shard.counts_all) else 0
+    if nmax > WINDOW_MAX_CLIPS:
+        raise ValueError(f"corpus_window_topk: videos of up to {WINDOW_MAX_CLIPS} clips, the corpus has one of {nmax}")
+    Nq = Q.shape[0]
+    rd = ri = unreachable = None
+    if own_global is not None and positives is not None:
+        own = np.asarray(own_global, np.int64).reshape(-1)
+        if len(own) != Nq:
+            raise ValueError(f"corpus_window_topk: {len(own)} own videos for {Nq} queries")
+        n_own = np.asarray(shard.counts_all, np.int64)[own]
+        R = len(positives)
+        if not 1 <= R <= 4:
+            raise ValueError(f"corpus_window_topk: {R} thresholds (1 .. 4 rank keys per query)")
+        keys = torch.full((R, Nq), KEY_INF, dtype=torch.int64, device=shard.device)
+        for r, rows in enumerate(positives):
+            rows = np.asarray(rows.cpu() if isinstance(rows, torch.Tensor) else rows, np.int64).reshape(-1, 3)
+            qi, s0, e0 = rows[:, 0], rows[:, 1], rows[:, 2]
+            if len(rows) and (qi.min() < 0 or qi.max() >= Nq or s0.min() < 0 or (e0 < s0).any() or (e0 >= n_own[qi]).any()):
+                raise ValueError("corpus_window_topk: a positive window does not lie inside its query's own video")
+            gv = own[qi] if len(rows) else qi
+            mine = (e0 - s0 < L) & (gv >= shard.lo) & (gv < shard.hi)
+            if not mine.any():
+                continue
+            items = torch.from_numpy(np.ascontiguousarray(np.stack([qi, gv, s0, e0], axis=1)[mine], dtype=np.int32)).to(shard.device)
+            kp = ops.window_span_keys(Q, shard.bank, items, vid_base=shard.lo)
+            keys[r].scatter_reduce_(0, items[:, 0].long(), kp, "amin")                 # the best positive window of each query
+        dist = _group(world)
+        if dist is not None:
+            dist.all_reduce(keys, op=dist.ReduceOp.MIN)
+        unreachable = keys == KEY_INF
+        rd, ri = _unpack_key(keys)
+        rd, ri = rd.contiguous(), ri.contiguous()
+    od, oi, cnt = _exchange(*ops.score_window(Q, shard.bank, L, k, rd, ri, workspace=workspace), k, ops, world)
+    vid = _video_of(shard, oi) if k > 0 else None
+    return od, oi, vid, cnt, unreachable
+
+
 def corpus_sentence_topk(shard: CorpusShard, S, probes, k, own_sentence=None, ops=None, world=1, workspace=None):
     """Sentence retrieval for moments over the corpus: per probe ``(global video, start_t, end_t)`` (inclusive clip span,
     ``utils.generate_moments`` units; host array-like [Nm, 3]) the k sentences of the bank ``S`` [Ns, D] with the smallest mean clip
@@ -1927,6 +2067,64 @@ class TorchCpuOps:
             keys = torch.stack(best, dim=1) if best else torch.zeros((Nq, 0), dtype=torch.int64)
         kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nq), rank_idx.reshape(-1, Nq))
         return self._topk_lists(keys, k) + (self._counts_below(keys, kstar, count_lt),)
+
+    def score_window(self, Q, bank, max_len, k, rank_dist=None, rank_idx=None, count_lt=None, workspace=None, eps=1e-6):
+        """Windowed retrieval (same semantics and bits as ``_vfr.score_window``): lane = flat start clip, a sequential float32 sum
+        over the next ``max_len`` end clips of the same video on the provider's one clip distance, one division, the canonical id.
+        Nothing is sized by n (n + 1) / 2 of a video."""
+        L = _check_window(max_len, "score_window")
+        counts = np.asarray(bank.counts, np.int64)
+        if len(counts) and int(counts.max()) > WINDOW_MAX_CLIPS:
+            raise ValueError(f"score_window: videos of up to {WINDOW_MAX_CLIPS} clips, the bank has one of {int(counts.max())}")
+        Nq = Q.shape[0]
+        off, mom = csr_offsets(counts)
+        vid = np.repeat(np.arange(len(counts)), counts)
+        s, n = np.arange(int(off[-1])) - off[vid], counts[vid]
+        d = self._clip_dist(Q, bank.emb, eps).numpy()
+        acc = d.copy()
+        parts = []
+        for i in range(L):
+            live = np.nonzero(s + i < n)[0]                                   # (nested: a start clip that ran out stays out)
+            if not len(live):
+                break
+            if i:
+                acc[:, live] = acc[:, live] + d[:, live + i]
+            sl, nl = s[live], n[live]
+            j = sl if i == 0 else nl + (sl * (2 * nl - sl - 1)) // 2 + (i - 1)
+            ids = torch.from_numpy(bank.id_base + mom[vid[live]] + j)
+            parts.append(_pack_key(torch.from_numpy(acc[:, live] / np.float32(i + 1)), ids[None, :].expand(Nq, len(live))))
+        keys = torch.cat(parts, dim=1) if parts else torch.zeros((Nq, 0), dtype=torch.int64)
+        kstar = None if rank_dist is None else _pack_key(rank_dist.reshape(-1, Nq), rank_idx.reshape(-1, Nq))
+        return self._topk_lists(keys, k) + (self._counts_below(keys, kstar, count_lt),)
+
+    def window_span_keys(self, Q, bank, items, vid_base=0, out=None, bad=None, eps=1e-6):
+        """Keys of named (query row, global video, start, end) spans (same semantics and bits as ``_vfr.window_span_keys``): items of
+        other shards and malformed ones (query row out of range, start < 0, end < start, end past the video, more than 64 clips)
+        are left untouched (KEY_INF pre-filled), the malformed ones set ``bad``."""
+        rows = [[int(x) for x in r] for r in torch.as_tensor(items).reshape(-1, 4).tolist()]
+        off = bank.clip_off.tolist()
+        mom = csr_offsets(bank.counts)[1]
+        Nv, Nq = len(off) - 1, Q.shape[0]
+        if out is None:
+            out = torch.full((len(rows),), KEY_INF, dtype=torch.int64)
+        for p, (q, gv, s0, e0) in enumerate(rows):
+            wrong = q < 0 or q >= Nq or s0 < 0 or e0 < s0 or e0 - s0 + 1 > WINDOW_MAX_LEN
+            lv = gv - vid_base
+            owned = 0 <= lv < Nv
+            if owned and e0 >= off[lv + 1] - off[lv]:
+                wrong = True
+            if wrong and bad is not None:
+                bad.fill_(1)
+            if wrong or not owned:
+                continue
+            n = off[lv + 1] - off[lv]
+            d = self._clip_dist(Q[q:q + 1], bank.emb[off[lv] + s0:off[lv] + e0 + 1], eps)[0]
+            acc = d[0]
+            for c in range(1, d.shape[0]):
+                acc = acc + d[c]
+            j = s0 if s0 == e0 else n + (s0 * (2 * n - s0 - 1)) // 2 + (e0 - s0 - 1)
+            out[p] = _pack_key((acc / float(e0 - s0 + 1)).reshape(1), torch.tensor([bank.id_base + int(mom[lv]) + j]))[0]
+        return out
 
     def score_sentences(self, S, bank, probes, k, vid_base=0, sent_base=0, rank_dist=None, rank_idx=None, count_lt=None, bad=None,
                         workspace=None, eps=1e-6):

@@ -561,3 +561,33 @@ def evaluate_prior(model, video_iterator, lang_iterator, annotations, device, ta
     if K:
         return out, (dist, idx, vid)
     return out
+
+
+def evaluate_windowed(model, video_iterator, lang_iterator, annotations, device, max_len, atk=(1, 10, 100), thresholds=(0.5, 0.7),
+                      agree=2, rank=0, world=1):
+    """Retrieval metrics over the WINDOW proposal set (``engine.corpus_window_topk``): the candidates are the moments of at most
+    ``max_len`` clips (1 .. 64), in videos of any length up to 1 024 clips -- how Charades-STA, ActivityNet Captions and TACoS are
+    searched; ``evaluate`` and the other entry points refuse a corpus with a video of more than 64 clips.
+
+    Per IoU threshold the 0-based rank of the best ground-truth-positive window among the candidates ->
+    ``{"model, IoU=<thr>": {"R@1", "R@10", "R@100", "MR"}}`` in ``evaluate``'s key format.  A window is positive when at least
+    ``agree`` annotators overlap it with IoU > the threshold (``engine.window_positives``, the strict rule of ``evaluate``).  A query
+    without a positive window is never found: its rank is the number of candidates; the share of such queries is
+    ``out["unreachable"] = {"IoU=<thr>": percent}`` -- 100 minus it is the recall ceiling of the proposal set.  With ``max_len`` >=
+    the longest video the "model" rows are ``evaluate``'s and every share is 0 (when every query has a positive moment).  The chance
+    and prior baselines of ``evaluate`` are not offered here."""
+    thresholds = list(thresholds)
+    with _eval_mode(model):
+        ops, _, annot_ids, shard, names, Q, own = _prepare(model, video_iterator, lang_iterator, device, rank, world)
+        if shard is None:
+            out = _fusion_empty("moments", atk, thresholds)
+            out["unreachable"] = {f"IoU={thr}": 0.0 for thr in thresholds}
+            return out
+        times = [annotations[a]["times"] for a in annot_ids]
+        positives = engine.window_positives(times, shard.counts_all[own], thresholds, max_len, strict=True, agree=agree)
+        _, _, _, ranks, unreach = engine.corpus_window_topk(shard, Q, max_len, 0, own_global=own, positives=positives, ops=ops,
+                                                            world=world)
+        ranks, unreach = ranks.cpu().numpy(), unreach.cpu().numpy()
+    out = {f"model, IoU={thr}": get_metrics(_rank_metrics(ranks[r], atk)) for r, thr in enumerate(thresholds)}
+    out["unreachable"] = {f"IoU={thr}": float(unreach[r].mean()) * 100 for r, thr in enumerate(thresholds)}
+    return out
